@@ -14,13 +14,16 @@ epilogues instead of a separate pass (`--no-norm-fold`).  Weak scaling: 2 sample
 (4 images 336x336 + 512 text tokens each -> merged length 2812), random-init weights, and a FRESH synthetic batch every step
 (the loss stays at ~ln V = 11.76, it cannot be memorised away, so the timed backward sees random-init operands).
 
+A plain run sets up, warms up, times the K steps (and writes their outputs with `--dump-outputs DIR`) and prints the line; `roofline`
+and `cpu_baseline` take runs of their own and are measured only with `--full` (null on a plain line).
+
 Prints ONE JSON line (rank 0) with the driver's fields plus
   ms_per_step_median / p10 / p90   per-step HIP-event durations over the K timed steps
-  roofline      dominant kernel (the bf16 MFMA GEMM family on the compute stream): algorithmic FLOPs / HIP-event time per launch,
+  roofline      (--full) dominant kernel (the bf16 MFMA GEMM family on the compute stream): algorithmic FLOPs / HIP-event time per launch,
                 live in the timed steps (`--gemm-table PATH` writes the per-shape table behind it); `traffic` and `mfma_busy_pct` need
                 PMC passes this run does not make and are null -- what the builder's own rocprofv3 passes of this command measured
                 (profiles/r05_pmc_step.json, tools/pmc_step_report.py) is carried under `pmc_static`
-  cpu_baseline  the oracle's CPU restatement of the same training_step ("port"), timed on this host's cores on a bounded
+  cpu_baseline  (--full) the oracle's CPU restatement of the same training_step ("port"), timed on this host's cores on a bounded
                 sample (1 sample, 1 ViT + {1,2} LLM layers + lm_head) and extrapolated linearly in depth; fp32 is `value`,
                 the bf16 leg is reported beside it
   dp            (N > 1) buckets / bytes per step and the time the compute stream waited for RCCL (exposed communication)
@@ -211,6 +214,37 @@ def write_gemm_table(path, entries, steps, config, step_ms):
         for lay, (u, fl) in sorted(by_lay.items()):
             fh.write(f"| {lay} | {u / steps / 1e3:.2f} | {fl / u / 1e6:.0f} | {fl / u / 1e6 / PEAK_BF16_TFLOPS:.3f} |\n")
         fh.write(f"| family | {fam_us / steps / 1e3:.2f} | {fam_fl / fam_us / 1e6:.0f} | {fam_fl / fam_us / 1e6 / PEAK_BF16_TFLOPS:.3f} |\n")
+
+
+DUMP_SAMPLE = 1 << 21           # elements of params.npy / grads.npy: 2 x 8 MB
+
+
+def dump_outputs(path, model, loss):
+    """`--dump-outputs`: what the last timed step handed its caller -- the loss, the trainable parameters after the optimizer update and
+    the gradients its backward left in the gradient arena (`.grad` views are dropped by zero_grad, the arena keeps them) -- as float32
+    .npy files.  Parameters and gradients are sampled at the same DUMP_SAMPLE flat positions over the trainable parameters in
+    named_parameters() order, drawn from a fixed seed, so two builds of the project compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    sizes = np.array([p.numel() for _, p in named], dtype=np.int64)
+    total = int(sizes.sum())
+    idx = np.arange(total) if total <= DUMP_SAMPLE else np.unique(np.random.default_rng(0).integers(0, total, DUMP_SAMPLE))
+    seg = np.searchsorted(np.cumsum(sizes), idx, side="right")
+    starts = np.cumsum(sizes) - sizes
+    grads = getattr(model, "_grad_views", None) or {}
+    ps, gs = [], []
+    with torch.no_grad():
+        for s in np.unique(seg):
+            n, p = named[s]
+            local = torch.from_numpy(idx[seg == s] - starts[s]).to(p.device)
+            ps.append(p.detach().reshape(-1)[local].float())
+            g = grads.get(n, p.grad)
+            gs.append(g.reshape(-1)[local].float() if g is not None else torch.full_like(ps[-1], float("nan")))
+    np.save(os.path.join(path, "loss.npy"), np.array([float(loss)], dtype=np.float32))
+    np.save(os.path.join(path, "params.npy"), torch.cat(ps).cpu().numpy())
+    np.save(os.path.join(path, "grads.npy"), torch.cat(gs).cpu().numpy())
 
 
 def cpu_baseline(cfg_name):
@@ -501,7 +535,16 @@ def main():
                          "HF's dataloader, get_batch_samples, the fused optimizer from create_optimizer, HF's scheduler / clip call / zero_grad), "
                          "after the native loop has been timed in the same process; the JSON line then describes the HF loop and carries the "
                          "native numbers and the difference under `native_loop` (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the instrumented steps behind `roofline` (--no-kernel-timer drops them) and "
+                         "the CPU baseline (--no-cpu-baseline drops it).  Without it both are null on the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as float32 .npy files to DIR: loss.npy, and a fixed "
+                         "seeded sample of the trainable parameters after the update (params.npy) and of the gradients of its backward "
+                         "(grads.npy), the same elements in both")
     args = ap.parse_args()
+    if (args.gemm_table or args.gemm_series) and not args.full:
+        ap.error("--gemm-table / --gemm-series come from the instrumented steps: add --full")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         _self_launch(args.gpus)
@@ -701,7 +744,9 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
-    timer = None if (args.no_kernel_timer or host_only) else []
+    if args.dump_outputs and rank == 0 and args.loop == "native":
+        dump_outputs(args.dump_outputs, model, losses[-1])
+    timer = None if (args.no_kernel_timer or host_only or not args.full) else []
     ms_with_timer = None
     n_extra = 0
     if timer is not None:
@@ -759,6 +804,8 @@ def main():
         elapsed, split, losses, _hf_timer, timed_batches, hf_trainer = run_hf_loop(args, model, batches, B, Event, sync, vmode)
         opt = hf_trainer._fused()
         fold = opt is not None
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, model, losses[-1])
     dp_devices = None
     if reducer is not None and dist.is_initialized():
         # every rank's device as the runtime names it (PCI bus id): N ranks must sit on N distinct GPUs
@@ -775,7 +822,7 @@ def main():
         ts_ms = [e[0].elapsed_time(e[1]) for e in split]
         pmc = None
         pmc_path = PMC_JSON_QWEN_FP8 if (qwen and precision == "fp8") else (None if (tiny or idefics or qwen) else PMC_JSON)
-        if pmc_path and os.path.exists(pmc_path):
+        if timer and pmc_path and os.path.exists(pmc_path):
             with open(pmc_path) as fh:
                 pmc = json.load(fh)
         roof = None
@@ -883,7 +930,7 @@ def main():
                             step_frac_of_peak_launched=round(t_roof / (ms * 1e-3), 4),
                             training_step_frac_of_peak_launched=round(t_roof / (_pct(ts_ms, 0.5) * 1e-3), 4))
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 if qwen:
                     cpu = cpu_baseline_qwen2vl(cfg, T, grids)

@@ -9,6 +9,16 @@ if ROOT not in sys.path:
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
+# The GPU checks run the data-parallel reducer's hardware-queue guard for real and expect the HIP runtime to come up with at least 8
+# hardware queues (check_dp_rccl_world1).  `import mantis_amd` only setdefaults GPU_MAX_HW_QUEUES=8, so a smaller value already in the
+# environment (ROCm's default is 4) would hold: the suite raises it here, before anything in the session initialises HIP.
+try:
+    _queues = int(os.environ.get("GPU_MAX_HW_QUEUES", ""))
+except ValueError:
+    _queues = 0
+if _queues < 8:
+    os.environ["GPU_MAX_HW_QUEUES"] = "8"
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")

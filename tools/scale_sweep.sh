@@ -30,7 +30,7 @@ for stage in $STAGES; do for algo in $ALGOS; do for ch in $CHANNELS; do for cus 
     if [ "$n" = 1 ] && { [ "$algo" != "${ALGOS%% *}" ] || [ "$ch" != "${CHANNELS%% *}" ]; }; then continue; fi
     envs="MANTIS_DP_ALGO=$algo MANTIS_GEMM_CUS=$cus"
     [ "$ch" != default ] && envs="$envs NCCL_MAX_NCHANNELS=$ch NCCL_MIN_NCHANNELS=$ch"
-    line=$(env $envs timeout 900 python bench.py --gpus $n --stage $stage --steps $STEPS --warmup $WARMUP --no-cpu-baseline 2>$O/scale_sweep.err | tail -1)
+    line=$(env $envs timeout 900 python bench.py --full --gpus $n --stage $stage --steps $STEPS --warmup $WARMUP --no-cpu-baseline 2>$O/scale_sweep.err | tail -1)
     [ -z "$line" ] && { echo "FAILED: $envs --gpus $n (see $O/scale_sweep.err)" >&2; continue; }
     python - "$algo" "$ch" "$cus" "$line" "$stage" >> $O/scale_sweep.jsonl <<'PY'
 import json, sys
