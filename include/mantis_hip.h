@@ -251,6 +251,17 @@ int mantis_attn_bwd(const void* Q, const void* K, const void* V, const void* O, 
                     void* workspace, int B, int L, int H, int Hkv, int hd, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ld_out,
                     int64_t ldo, int64_t lddq, int64_t lddk, int64_t lddv, float scale, int causal, void* stream);
 int mantis_attn_bwd_needs_workspace(int H, int Hkv, int hd);
+/* Sliding-window causal attention (Mistral, HF:models/mistral/modeling_mistral.py sliding_window): query q attends key k iff
+ * q - window < k <= q, the key is live in kmask and (packed rows, kstart / qend as above) in q's own sample.  Arguments as
+ * mantis_attn_fwd / mantis_attn_bwd plus window (>= 1; causal must be 1).  The bounds are computed inside the kernels: the band's
+ * lower edge is a second diagonal (only the tiles it cuts are masked).  window >= L runs mantis_attn_fwd / _bwd's kernels (same bits). */
+int mantis_attn_fwd_window(const void* Q, const void* K, const void* V, const int32_t* kmask, const int32_t* kstart, void* O, float* LSE,
+                           int B, int L, int H, int Hkv, int hd, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float scale,
+                           int causal, int window, void* stream);
+int mantis_attn_bwd_window(const void* Q, const void* K, const void* V, const void* O, const void* dO, const int32_t* kmask,
+                           const int32_t* kstart, const int32_t* qend, const float* LSE, float* Dsum, void* dQ, void* dK, void* dV,
+                           void* workspace, int B, int L, int H, int Hkv, int hd, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ld_out,
+                           int64_t ldo, int64_t lddq, int64_t lddk, int64_t lddv, float scale, int causal, int window, void* stream);
 
 /* ---- loss: modeling_llava.py:521-537 (shift + mask filter resolved by mantis_pack_plan into ce_row / ce_tgt).
  * count_out is int32[2]: [0] rows with 0 <= target < V (the mean's denominator), [1] rows with target >= V (torch's

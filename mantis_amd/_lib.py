@@ -56,6 +56,8 @@ SIGNATURES = {
     "mantis_attn_dsum": [P, P, P, I, I, I, I, L, P],
     "mantis_attn_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L, L, L, L, L, L, L, L, F, I, P],
     "mantis_attn_bwd_needs_workspace": [I, I, I],
+    "mantis_attn_fwd_window": [P, P, P, P, P, P, P, I, I, I, I, I, L, L, L, L, F, I, I, P],
+    "mantis_attn_bwd_window": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L, L, L, L, L, L, L, L, F, I, I, P],
     "mantis_attn_fwd_cross": [P, P, P, P, P, P, I, I, I, I, I, I, L, L, L, L, F, P],
     "mantis_attn_bwd_cross": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, L, L, L, L, L, L, L, L, F, P],
     "mantis_ce_fwd_bwd": [P, P, I, I, L, F, F, I, P, P, P, P, P],

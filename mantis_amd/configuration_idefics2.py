@@ -3,13 +3,15 @@
 and nesting (vision_config / perceiver_config / text_config dicts), without the transformers dependency."""
 from .configuration_llava import SubConfig
 
+MISTRAL_SLIDING_WINDOW = 4096      # HF MistralConfig default (Mistral-7B)
+
 _VISION = dict(hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12, num_channels=3, image_size=224,
                patch_size=32, hidden_act="gelu_pytorch_tanh", layer_norm_eps=1e-6, attention_dropout=0.0)
 _PERCEIVER = dict(hidden_act="silu", resampler_n_latents=64, resampler_depth=3, resampler_n_heads=16, resampler_head_dim=96,
                   num_key_value_heads=4, attention_dropout=0.0)
 _TEXT = dict(model_type="mistral", hidden_size=4096, intermediate_size=14336, num_hidden_layers=32, num_attention_heads=32,
              num_key_value_heads=8, vocab_size=32000, rope_theta=10000.0, rms_norm_eps=1e-5, hidden_act="silu", head_dim=None,
-             sliding_window=None, initializer_range=0.02, tie_word_embeddings=False, attention_bias=False, mlp_bias=False)
+             initializer_range=0.02, tie_word_embeddings=False, attention_bias=False, mlp_bias=False)
 
 
 class Idefics2Config:
@@ -39,11 +41,15 @@ class Idefics2Config:
             raise NotImplementedError("only the default RoPE is implemented on this path")
         if p["attention_dropout"] or v["attention_dropout"]:
             raise NotImplementedError("attention dropout is not implemented (Idefics2-8B uses 0.0)")
-        if t.get("sliding_window") not in (None, 0) and t["sliding_window"] < 1 << 30:
-            # Mistral's 4096-token window: identical to full causal attention for sequences up to the window
-            self.sliding_window = int(t["sliding_window"])
+        if "sliding_window" not in t:
+            # the backbone's own default: HF MistralConfig.sliding_window = 4096, LlamaConfig has none.  An explicit None keeps full
+            # causal attention.
+            t["sliding_window"] = MISTRAL_SLIDING_WINDOW if t["model_type"] == "mistral" else None
+        if t["sliding_window"] not in (None, 0) and t["sliding_window"] < 1 << 30:
+            t["sliding_window"] = int(t["sliding_window"])     # query q attends keys q - W < k <= q (decoder.attn_window)
         else:
-            self.sliding_window = None
+            t["sliding_window"] = None
+        self.sliding_window = t["sliding_window"]
         self.vision_config, self.perceiver_config, self.text_config = SubConfig(**v), SubConfig(**p), SubConfig(**t)
         self.image_token_id = image_token_id
         self.vocab_size = t["vocab_size"]
@@ -71,5 +77,6 @@ def mantis_8b_idefics2():
                            patch_size=14),
         perceiver_config=dict(resampler_n_latents=64, resampler_depth=3, resampler_n_heads=16, resampler_head_dim=96, num_key_value_heads=4),
         text_config=dict(model_type="mistral", hidden_size=4096, intermediate_size=14336, num_hidden_layers=32, num_attention_heads=32,
-                         num_key_value_heads=8, vocab_size=32003, rope_theta=10000.0, rms_norm_eps=1e-5),
+                         num_key_value_heads=8, vocab_size=32003, rope_theta=10000.0, rms_norm_eps=1e-5,
+                         sliding_window=MISTRAL_SLIDING_WINDOW),
         image_token_id=32001)

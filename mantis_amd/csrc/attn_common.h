@@ -16,6 +16,9 @@ __device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) {
     return c.b;
 }
 
+// sliding window W: the lower key bound of query row `row` whose other bound (packed sample start, or 0) is ks: max(ks, row - W + 1)
+__device__ __forceinline__ int win_lo(int row, int ks, int W) { return row - W + 1 > ks ? row - W + 1 : ks; }
+
 template <int HD>
 struct AttnCfg {
     static constexpr int KP = (HD + 15) / 16 * 16;   // contraction length of Q.K^T, zero padded

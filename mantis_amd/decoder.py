@@ -16,6 +16,20 @@ def inv_freq(head_dim, theta):
     return 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.float32) / head_dim))
 
 
+def attn_window(tc, L):
+    """The sliding window of the text backbone's attention if it changes the result for rows of length L, else None: query q attends
+    keys q - W < k <= q (Mistral, HF:models/mistral/modeling_mistral.py create_sliding_window_causal_mask); engaged only when L > W,
+    so rows up to the window run exactly the plain causal path.  Qwen2 configs carry a `sliding_window` that their
+    use_sliding_window=False switches off."""
+    w = tc.get("sliding_window") if tc.get("use_sliding_window", True) else None
+    return w if w is not None and L > w else None
+
+
+def _window_kw(tc, L):
+    w = attn_window(tc, L)
+    return {} if w is None else dict(window=w)
+
+
 def layer_forward(K, lw, tc, x, B, L, cos, sin, kmask, kstart, scale):
     """One decoder block: x [B*L, d] -> (x_out, what its backward reads).  Deterministic (fixed summation orders everywhere): running it
     again on the same x gives the same bits, which is what activation checkpointing relies on."""
@@ -23,7 +37,7 @@ def layer_forward(K, lw, tc, x, B, L, cos, sin, kmask, kstart, scale):
     eps = tc.rms_norm_eps
     n1, rstd1 = K.rmsnorm_fwd(x, lw["ln1"], eps)
     qkv = K.linear_qkv_rope(n1, lw["qkv"], lw.get("qkv_b"), cos, sin, H + Hkv, hd)      # RoPE in the projection's epilogue (hd 128)
-    o, lse = K.attn_fwd(qkv, B, L, H, Hkv, hd, kmask, scale, True, kstart=kstart)
+    o, lse = K.attn_fwd(qkv, B, L, H, Hkv, hd, kmask, scale, True, kstart=kstart, **_window_kw(tc, L))
     x_mid = K.gemm_nt(o, lw["o"], residual=x)
     n2, rstd2 = K.rmsnorm_fwd(x_mid, lw["ln2"], eps)
     gu, a = K.linear_gu_swiglu(n2, lw["gu"])                                            # SwiGLU in the projection's epilogue
@@ -193,7 +207,7 @@ def decoder_backward(K, lm, grads, grads_layers, tc, ctx, hctx, plan, B, L, kmas
         if lg_["o"] is not None:
             off_path(lambda dx_mid=dx_mid, o=o: K.linear_dw(dx_mid, o, lg_["o"], acc), dx_mid, o)
         do = K.linear_dx(dx_mid, lw["o"])
-        dqkv = K.attn_bwd(qkv, o, do, lse, B, L, H, Hkv, hd, kmask, scale, True, kstart=kstart, qend=qend)
+        dqkv = K.attn_bwd(qkv, o, do, lse, B, L, H, Hkv, hd, kmask, scale, True, kstart=kstart, qend=qend, **_window_kw(tc, L))
         del do, o
         K.rope_apply_(dqkv, cos, sin, H + Hkv, hd, backward=True)
         if held is not None:

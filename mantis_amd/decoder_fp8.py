@@ -64,7 +64,7 @@ def layer_forward(K, lw, w8, i, tc, x, B, L, cos, sin, kmask, kstart, scale, par
     n1q = _quant(K, n1, E4M3, keep, parts, rw)
     qkv = _lin(K, n1q, w8.get(K, i, "qkv"), bias=lw.get("qkv_b"))
     K.rope_apply_(qkv, cos, sin, H + Hkv, hd)
-    o, lse = K.attn_fwd(qkv, B, L, H, Hkv, hd, kmask, scale, True, kstart=kstart)
+    o, lse = K.attn_fwd(qkv, B, L, H, Hkv, hd, kmask, scale, True, kstart=kstart, **D._window_kw(tc, L))
     oq = _quant(K, o, E4M3, keep, None, rw)
     x_mid = _lin(K, oq, w8.get(K, i, "o"), residual=x)
     n2, rstd2 = K.rmsnorm_fwd(x_mid, lw["ln2"], eps, amax_parts=parts)
@@ -175,7 +175,7 @@ def decoder_backward(K, lm, w8, grads, grads_layers, tc, ctx, hctx, plan, B, L, 
         dw(dmq, oq, lg_["o"])
         do = _dx(K, dmq, w8.get(K, i, "o"))
         del dmq, oq
-        dqkv = K.attn_bwd(qkv, o, do, lse, B, L, H, Hkv, hd, kmask, scale, True, kstart=kstart, qend=qend)
+        dqkv = K.attn_bwd(qkv, o, do, lse, B, L, H, Hkv, hd, kmask, scale, True, kstart=kstart, qend=qend, **D._window_kw(tc, L))
         del do, o
         K.rope_apply_(dqkv, cos, sin, H + Hkv, hd, backward=True)
         dqq = _quant(K, dqkv, E5M2, lg_["qkv"] is not None, None, rw)

@@ -549,28 +549,46 @@ def rope_apply_(x, cos, sin, nheads, hd, backward=False):
     return x
 
 
-def attn_fwd_qkv(q, k, v, B, Lseq, H, Hkv, hd, kmask, scale, causal, want_lse=True, kstart=None, out=None):
+def window_engaged(window, Lseq):
+    """The sliding window changes the result only when a row is longer than it: `window` None or >= Lseq is plain causal attention."""
+    return window is not None and window < Lseq
+
+
+def attn_fwd_qkv(q, k, v, B, Lseq, H, Hkv, hd, kmask, scale, causal, want_lse=True, kstart=None, out=None, window=None):
     """q [B*L, >=H*hd], k / v [B*L, >=Hkv*hd] bf16 row views (any row stride, heads contiguous inside a row; they may be column
-    slices of one fused projection output).  Returns o [B*L, H*hd], lse [B,H,L] fp32."""
+    slices of one fused projection output).  Returns o [B*L, H*hd], lse [B,H,L] fp32.
+    window (causal only): sliding window W -- query q attends keys q - W < k <= q (Mistral); engaged when W < Lseq."""
     _chk2d(q, "q"), _chk2d(k, "k"), _chk2d(v, "v")
     o = torch.empty((B * Lseq, H * hd), dtype=BF16, device=q.device) if out is None else out     # `out`: a row view of a larger buffer
     lse = torch.empty((B, H, Lseq), dtype=torch.float32, device=q.device) if want_lse else None
-    rc = _L.mantis_attn_fwd(_p(q), _p(k), _p(v), _p(kmask), _p(kstart), _p(o), _p(lse), B, Lseq, H, Hkv, hd, q.stride(0), k.stride(0),
-                            v.stride(0), o.stride(0), float(scale), int(causal), _stream())
+    if window_engaged(window, Lseq):
+        rc = _L.mantis_attn_fwd_window(_p(q), _p(k), _p(v), _p(kmask), _p(kstart), _p(o), _p(lse), B, Lseq, H, Hkv, hd, q.stride(0),
+                                       k.stride(0), v.stride(0), o.stride(0), float(scale), int(causal), int(window), _stream())
+    else:
+        rc = _L.mantis_attn_fwd(_p(q), _p(k), _p(v), _p(kmask), _p(kstart), _p(o), _p(lse), B, Lseq, H, Hkv, hd, q.stride(0), k.stride(0),
+                                v.stride(0), o.stride(0), float(scale), int(causal), _stream())
     _lib.check(rc, f"attn_fwd hd={hd}")
     return o, lse
 
 
-def attn_bwd_qkv(q, k, v, o, do, lse, dq, dk, dv, B, Lseq, H, Hkv, hd, kmask, scale, causal, kstart=None, qend=None, no_workspace=False):
+def attn_bwd_qkv(q, k, v, o, do, lse, dq, dk, dv, B, Lseq, H, Hkv, hd, kmask, scale, causal, kstart=None, qend=None, no_workspace=False,
+                 window=None):
     """Gradients w.r.t. q, k, v written into the given row views dq [B*L, H*hd], dk / dv [B*L, Hkv*hd] (any row stride).
-    no_workspace (tests): withhold the per-query-head workspace, which holds GQA geometries to the group dK/dV kernel where it exists."""
+    no_workspace (tests): withhold the per-query-head workspace, which holds GQA geometries to the group dK/dV kernel where it exists.
+    window: as attn_fwd_qkv (the same value the forward was given)."""
     dsum = torch.empty((B, H, Lseq), dtype=torch.float32, device=q.device)     # rowsum(dO * O): filled by the dQ kernel
     ws = torch.empty((2, B * Lseq, H * hd), dtype=BF16, device=q.device) if (_L.mantis_attn_bwd_needs_workspace(H, Hkv, hd) and
                                                                               not no_workspace) else None
-    rc = _L.mantis_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(kmask), _p(kstart), _p(qend), _p(lse), _p(dsum), _p(dq), _p(dk),
-                            _p(dv), _p(ws), B, Lseq,
-                            H, Hkv, hd, q.stride(0), k.stride(0), v.stride(0), o.stride(0), do.stride(0), dq.stride(0), dk.stride(0),
-                            dv.stride(0), float(scale), int(causal), _stream())
+    if window_engaged(window, Lseq):
+        rc = _L.mantis_attn_bwd_window(_p(q), _p(k), _p(v), _p(o), _p(do), _p(kmask), _p(kstart), _p(qend), _p(lse), _p(dsum), _p(dq),
+                                       _p(dk), _p(dv), _p(ws), B, Lseq, H, Hkv, hd, q.stride(0), k.stride(0), v.stride(0), o.stride(0),
+                                       do.stride(0), dq.stride(0), dk.stride(0), dv.stride(0), float(scale), int(causal), int(window),
+                                       _stream())
+    else:
+        rc = _L.mantis_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(kmask), _p(kstart), _p(qend), _p(lse), _p(dsum), _p(dq), _p(dk),
+                                _p(dv), _p(ws), B, Lseq,
+                                H, Hkv, hd, q.stride(0), k.stride(0), v.stride(0), o.stride(0), do.stride(0), dq.stride(0), dk.stride(0),
+                                dv.stride(0), float(scale), int(causal), _stream())
     _lib.check(rc, f"attn_bwd hd={hd}")
 
 
@@ -600,21 +618,21 @@ def _split_qkv(qkv, H, Hkv, hd):
     return qkv[:, : H * hd], qkv[:, H * hd: (H + Hkv) * hd], qkv[:, (H + Hkv) * hd: (H + 2 * Hkv) * hd]
 
 
-def attn_fwd(qkv, B, Lseq, H, Hkv, hd, kmask, scale, causal, want_lse=True, kstart=None):
+def attn_fwd(qkv, B, Lseq, H, Hkv, hd, kmask, scale, causal, want_lse=True, kstart=None, window=None):
     """qkv: [B*L, (H+2Hkv)*hd] fused projection output (q | k | v).  Returns o [B*L, H*hd], lse [B,H,L].
-    kstart int32 [B,L] (packed samples): first key position each query may attend."""
+    kstart int32 [B,L] (packed samples): first key position each query may attend.  window: see attn_fwd_qkv."""
     _chk2d(qkv, "qkv")
     q, k, v = _split_qkv(qkv, H, Hkv, hd)
-    return attn_fwd_qkv(q, k, v, B, Lseq, H, Hkv, hd, kmask, scale, causal, want_lse, kstart=kstart)
+    return attn_fwd_qkv(q, k, v, B, Lseq, H, Hkv, hd, kmask, scale, causal, want_lse, kstart=kstart, window=window)
 
 
-def attn_bwd(qkv, o, do, lse, B, Lseq, H, Hkv, hd, kmask, scale, causal, kstart=None, qend=None, no_workspace=False):
+def attn_bwd(qkv, o, do, lse, B, Lseq, H, Hkv, hd, kmask, scale, causal, kstart=None, qend=None, no_workspace=False, window=None):
     """Returns dqkv [B*L, (H+2Hkv)*hd] (gradient w.r.t. the post-RoPE q, k and v)."""
     dqkv = torch.empty_like(qkv)
     q, k, v = _split_qkv(qkv, H, Hkv, hd)
     dq, dk, dv = _split_qkv(dqkv, H, Hkv, hd)
     attn_bwd_qkv(q, k, v, o, do, lse, dq, dk, dv, B, Lseq, H, Hkv, hd, kmask, scale, causal, kstart=kstart, qend=qend,
-                 no_workspace=no_workspace)
+                 no_workspace=no_workspace, window=window)
     return dqkv
 
 

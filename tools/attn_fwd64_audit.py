@@ -23,11 +23,13 @@ def main():
                    stderr=subprocess.DEVNULL)
     bad, scratch, in_asm, kernel = [], 0, False, None
     hist = {}
+    per = {}                                 # kernel -> [AGPR / v192+ uses outside asm, scratch instructions]
     for n, line in enumerate(open(out), 1):
         t = line.strip()
-        m = re.match(r"^(_Z\w*attn_fwd64_kernel\w*):", t)
+        m = re.match(r"^(_Z\w*attn_fwd64_\w*kernel\w*):", t)      # attn_fwd64_kernel<CAUSAL> and attn_fwd64_win_kernel
         if m:
             kernel = m.group(1)
+            per.setdefault(kernel, [0, 0])
         if kernel is None:
             continue
         if t.startswith(";;#ASMSTART"):
@@ -44,14 +46,22 @@ def main():
         if not in_asm:
             if "v_accvgpr" in t or re.search(r"\ba\[?\d+", t.split(";")[0]):
                 bad.append((n, t))
+                per[kernel][0] += 1
             if "scratch_" in t:
                 scratch += 1
+                per[kernel][1] += 1
             code = t.split(";")[0]
             regs = [int(m.group(1)) for m in re.finditer(r"\bv(\d+)\b", code)]
             for m in re.finditer(r"\bv\[(\d+):(\d+)\]", code):
                 regs += [int(m.group(1)), int(m.group(2))]
             if any(r >= 192 for r in regs):
                 bad.append((n, "v192+ outside asm: " + t))
+                per[kernel][0] += 1
+    for k, (nb, ns) in sorted(per.items()):
+        print(f"  {k}: compiler AGPR uses outside asm {nb}, scratch instructions {ns}")
+    if len(per) < 3:                         # both attn_fwd64_kernel instantiations and attn_fwd64_win_kernel
+        print(f"expected 3 kernels in the listing, found {sorted(per)}")
+        sys.exit(1)
     print(f"compiler AGPR uses outside asm: {len(bad)}; scratch instructions: {scratch}")
     for n, t in bad[:20]:
         print(f"  {n}: {t}")
