@@ -270,6 +270,28 @@ int mantis_ce_fwd_bwd(void* logits, const int32_t* targets, int R, int V, int64_
                       int write_grad, float* row_loss_ws, float* row_lse_out /*nullable*/, int32_t* count_out,
                       float* loss_out, void* stream);
 
+/* ---- sequence classification / regression head (csrc/seqcls.hip): the tail of the reference's Idefics2ForSequenceClassification.forward
+ * (/root/reference/mantis/models/idefics2/modeling_idefics2.py:2165-2211) on the B pooled rows only; the [B, T, C] logits are never formed.
+ * 1 <= C <= 128, d % 8 == 0, d <= 8192, else the invalid-argument code.  problem_type: 0 regression (MSE), 1 single-label (cross-entropy,
+ * labels int32 [B]), 2 multi-label (BCE with logits); 0 and 2 take labels float [B, C].  All losses are means; fp32 arithmetic, fixed
+ * summation orders. */
+/* out[b] = (first t with input_ids[b, t] == pad_id) - 1 mod T: T - 1 for a row without the pad id or starting with it; has_pad = 0: T - 1 */
+int mantis_seqcls_pool_index(const int64_t* input_ids, int B, int T, int64_t pad_id, int has_pad, int32_t* out, void* stream);
+/* x bf16 [B*T, d] = the decoder output BEFORE the final norm.  Writes nf bf16 [B, d] (normalised pooled rows), rstd [B], rows int32 [B]
+ * (= b*T + pool[b]), pooled_logits fp32 [B, C]; with labels (nullable): loss_out[0] = loss_scale * mean loss, status_out[0] = samples whose
+ * class label is outside [0, C) (they add neither loss nor gradient; torch raises), and (write_grad) dlogits fp32 [B, C] =
+ * d(grad_scale * mean loss) / d pooled_logits.  row_ws: 2*B floats. */
+int mantis_seqcls_head_fwd(const void* x, const int32_t* pool, const void* norm_weight, const void* score_weight, const void* score_bias,
+                           const void* labels /*nullable*/, int problem_type, int B, int T, int d, int C, float eps, float grad_scale,
+                           float loss_scale, int write_grad, void* nf, float* rstd, int32_t* rows, float* pooled_logits, float* dlogits,
+                           float* row_ws, float* loss_out, int32_t* status_out, void* stream);
+/* grad_score_weight [C, d] (+)= dlogits^T nf, grad_score_bias [C] (+)= column sums, grad_norm_weight [d] (+)= RMSNorm weight gradient
+ * (each nullable, sums over b in index order), dx_rows bf16 [B, d] = gradient w.r.t. the pooled rows of x (rows < n_rows = rows of x).
+ * workspace: B*d floats. */
+int mantis_seqcls_head_bwd(const float* dlogits, const void* nf, const void* x, const int32_t* rows, int64_t n_rows, const float* rstd,
+                           const void* norm_weight, const void* score_weight, int B, int d, int C, void* grad_score_weight,
+                           void* grad_score_bias, void* grad_norm_weight, int accumulate, void* dx_rows, float* workspace, void* stream);
+
 /* ---- ViT front end: modeling_llava.py:434-435 + HF Siglip/CLIP VisionEmbeddings; feature select modeling_llava.py:460-461 */
 int mantis_im2col(const float* pixels, void* patches, int I, int C, int H, int W, int P, int Kp, void* stream);
 /* Qwen2-VL PatchEmbed input (HF:models/qwen2_vl/modeling_qwen2_vl.py:268-274): fp32 flattened patches -> bf16 rows zero-padded to Kp */

@@ -61,6 +61,9 @@ SIGNATURES = {
     "mantis_attn_fwd_cross": [P, P, P, P, P, P, I, I, I, I, I, I, L, L, L, L, F, P],
     "mantis_attn_bwd_cross": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, L, L, L, L, L, L, L, L, F, P],
     "mantis_ce_fwd_bwd": [P, P, I, I, L, F, F, I, P, P, P, P, P],
+    "mantis_seqcls_pool_index": [P, I, I, L, I, P, P],
+    "mantis_seqcls_head_fwd": [P, P, P, P, P, P, I, I, I, I, I, F, F, F, I, P, P, P, P, P, P, P, P, P],
+    "mantis_seqcls_head_bwd": [P, P, P, P, L, P, P, P, I, I, I, P, P, P, I, P, P, P],
     "mantis_im2col": [P, P, I, I, I, I, I, I, P],
     "mantis_cast_pad_rows": [P, P, L, I, L, I, P],
     "mantis_vit_assemble": [P, P, P, P, I, I, I, P],

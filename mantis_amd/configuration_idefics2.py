@@ -54,25 +54,45 @@ class Idefics2Config:
         self.image_token_id = image_token_id
         self.vocab_size = t["vocab_size"]
         self.use_return_dict = kwargs.pop("use_return_dict", True)
+        # sequence classification (Idefics2ForSequenceClassification), HF PretrainedConfig's semantics: num_labels (default 2),
+        # problem_type one of PROBLEM_TYPES or None (= inferred from num_labels and the label dtype at the first forward with labels),
+        # pad_token_id of the TOP-LEVEL config (the pooled position is taken from it; None: batch size 1 only)
+        num_labels = kwargs.pop("num_labels", 2)
+        if isinstance(num_labels, bool) or not isinstance(num_labels, int) or num_labels < 1:
+            raise ValueError(f"num_labels must be a positive integer, got {num_labels!r}")
+        self.num_labels = num_labels
+        problem_type = kwargs.pop("problem_type", None)
+        if problem_type is not None and problem_type not in PROBLEM_TYPES:
+            raise ValueError(f"The config parameter `problem_type` was not understood: received {problem_type} but only "
+                             f"'regression', 'single_label_classification' and 'multi_label_classification' are valid.")
+        self.problem_type = problem_type
+        pad = kwargs.pop("pad_token_id", None)
+        self.pad_token_id = None if pad is None else int(pad)
         for k, val in kwargs.items():
             setattr(self, k, val)
 
     def to_dict(self):
         return dict(vision_config=self.vision_config.to_dict(), perceiver_config=self.perceiver_config.to_dict(),
-                    text_config=self.text_config.to_dict(), image_token_id=self.image_token_id)
+                    text_config=self.text_config.to_dict(), image_token_id=self.image_token_id, num_labels=self.num_labels,
+                    problem_type=self.problem_type, pad_token_id=self.pad_token_id)
 
     @classmethod
     def from_oracle_meta(cls, meta):
-        """Build from the json blob stored in tests/golden/weights_idefics2.npz."""
+        """Build from the json blob stored in tests/golden/weights_idefics2.npz (+ the optional classification fields)."""
+        extra = {k: meta[k] for k in ("num_labels", "problem_type", "pad_token_id") if k in meta}
         return cls(vision_config=dict(meta["vision"]), perceiver_config=dict(meta["perceiver"]), text_config=dict(meta["text"]),
-                   image_token_id=meta["image_token_id"])
+                   image_token_id=meta["image_token_id"], **extra)
 
 
-def mantis_8b_idefics2():
+PROBLEM_TYPES = ("regression", "single_label_classification", "multi_label_classification")
+
+
+def mantis_8b_idefics2(**kwargs):
     """BASELINE.json configs[3]: Mantis-8B-Idefics2 = SigLIP-so400m/14 NaViT (980-px canvas: 70 x 70 position buckets) + perceiver
     resampler (64 latents, depth 3, 16/4 heads x 96) + Mistral-7B (+3 added tokens: <fake_token_around_image> 32000, <image> 32001,
-    <end_of_utterance> 32002)."""
-    return Idefics2Config(
+    <end_of_utterance> 32002).  kwargs: the classification fields (num_labels, problem_type, pad_token_id; the reference's scorer
+    runs set problem_type="regression", num_labels=5)."""
+    return Idefics2Config(**kwargs,
         vision_config=dict(hidden_size=1152, intermediate_size=4304, num_hidden_layers=27, num_attention_heads=16, image_size=980,
                            patch_size=14),
         perceiver_config=dict(resampler_n_latents=64, resampler_depth=3, resampler_n_heads=16, resampler_head_dim=96, num_key_value_heads=4),

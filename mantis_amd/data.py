@@ -97,6 +97,53 @@ class Collator:
         return batch
 
 
+def collate_classification(samples, pad_token_id):
+    """Batch for the sequence-classification / regression head (`Idefics2ForSequenceClassification`).  samples: what the reference's
+    `ClassificationDataset.__getitem__` emits (/root/reference/mantis/train/data.py:1270-1293): `input_ids` [1, T_i] (or [T_i]),
+    optional `attention_mask`, `labels` float [1, C] (one row of target scores; integer class ids [1] for single-label), `pixel_values`
+    [1, n_i, 3, H, W], optional `pixel_attention_mask` [1, n_i, H, W].  -> input_ids / attention_mask int64 [B, T_max] RIGHT-padded with
+    pad_token_id / 0 (the pooled position is the token before the first pad id), labels [B, C] float32 (or [B] int64), pixel_values
+    [B, n_max, 3, H, W] with all-zero images where a sample has fewer (the model drops those).  Any batch size: the reference's collator
+    is limited to one sample."""
+    ids = [_row(s["input_ids"]) for s in samples]
+    B, T = len(ids), max(len(x) for x in ids)
+    out_ids = np.full((B, T), pad_token_id, dtype=np.int64)
+    mask = np.zeros((B, T), dtype=np.int64)
+    for b, x in enumerate(ids):
+        out_ids[b, : len(x)] = x
+        am = samples[b].get("attention_mask")
+        mask[b, : len(x)] = 1 if am is None else _row(am)[: len(x)]
+    batch = dict(input_ids=torch.from_numpy(out_ids), attention_mask=torch.from_numpy(mask))
+    labs = [torch.as_tensor(s["labels"]) for s in samples if s.get("labels") is not None]
+    if labs:
+        if len(labs) != B:
+            raise ValueError("collate_classification: some samples carry labels and some do not")
+        if labs[0].dtype.is_floating_point:
+            batch["labels"] = torch.stack([x.reshape(-1).to(torch.float32) for x in labs])            # [B, C]
+        else:
+            batch["labels"] = torch.cat([x.reshape(-1).to(torch.int64) for x in labs])                # [B] class ids
+            if batch["labels"].numel() != B:
+                raise ValueError("collate_classification: integer labels are one class id per sample")
+    pvs = [None if s.get("pixel_values") is None else torch.as_tensor(s["pixel_values"], dtype=torch.float32) for s in samples]
+    if any(p is not None for p in pvs):
+        ref = next(p for p in pvs if p is not None)
+        n_max = max(p.shape[1] for p in pvs if p is not None)
+        pv = torch.zeros((B, n_max, *ref.shape[2:]), dtype=torch.float32)
+        pms = [s.get("pixel_attention_mask") for s in samples]
+        pm = torch.ones((B, n_max, *ref.shape[3:]), dtype=torch.bool) if any(m is not None for m in pms) else None
+        for b, p in enumerate(pvs):
+            if p is None:
+                continue
+            pv[b, : p.shape[1]] = p[0]
+            if pm is not None and pms[b] is not None:
+                pm[b, : p.shape[1]] = torch.as_tensor(pms[b]).bool()[0]
+        batch["pixel_values"] = pv
+        batch["pixel_attention_mask"] = pm
+    else:
+        batch["pixel_values"] = batch["pixel_attention_mask"] = None
+    return batch
+
+
 def _row(x, dtype=np.int64):
     a = np.asarray(x.numpy() if isinstance(x, torch.Tensor) else x, dtype=dtype)
     return a.reshape(-1)

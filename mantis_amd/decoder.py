@@ -148,14 +148,62 @@ def head_backward(K, lm, grads, hctx, plan, B, L, acc, on_bucket_ready=None):
     return dx
 
 
+SEQCLS_PROBLEM_TYPES = ("regression", "single_label_classification", "multi_label_classification")
+
+
+def seqcls_pool_positions(input_ids, pad_token_id):
+    """The pooled position of every row as the reference's sequence-classification heads take it (HF *ForSequenceClassification;
+    /root/reference/mantis/models/idefics2/modeling_idefics2.py:2174-2187), as host arithmetic on input_ids [B, T] -> int64 [B]:
+    (first occurrence of pad_token_id) - 1 mod T -- T - 1 for a row without the pad id AND for a row that starts with it (left padding:
+    the rule looks at input_ids, not at attention_mask).  pad_token_id None: T - 1 for B == 1, the reference's ValueError otherwise."""
+    B, T = input_ids.shape
+    if pad_token_id is None:
+        if B != 1:
+            raise ValueError("Cannot handle batch sizes > 1 if no padding token is defined.")
+        return torch.full((B,), T - 1, dtype=torch.int64)
+    return (torch.eq(input_ids, pad_token_id).int().argmax(-1) - 1) % T
+
+
+def seqcls_head_and_loss(K, lm, tc, x, input_ids_dev, pad_token_id, labels, problem_type, B, L, grad_scale, loss_scale, compute_grads):
+    """Classification counterpart of head_and_loss: final norm + score linear (with bias) + MSE / cross-entropy / BCE-with-logits on the B
+    pooled rows only (the [B, L, C] logits of the reference are never formed: nothing but logits[b, t_b] reaches the output or the
+    loss).  labels: float32 [B, C] | int32 [B] on the device, or None.  Returns (loss, pooled logits fp32 [B, C], status, ctx, pooled
+    positions int32 [B]); status[0] = samples with a class label outside [0, C)."""
+    if pad_token_id is None and B != 1:
+        raise ValueError("Cannot handle batch sizes > 1 if no padding token is defined.")
+    pool = K.seqcls_pool_index(input_ids_dev, pad_token_id)
+    r = K.seqcls_head_fwd(x, pool, lm["norm"], lm["score_w"], lm["score_b"], labels, problem_type, B, L, tc.rms_norm_eps, grad_scale,
+                          loss_scale, write_grad=compute_grads)
+    ctx = None
+    if compute_grads:
+        ctx = dict(seqcls=True, dlogits=r["dlogits"], nf=r["nf"], rstd=r["rstd"], rows=r["rows"], x=x)
+    return r["loss"], r["logits"], r["status"], ctx, pool
+
+
+def seqcls_head_backward(K, lm, grads, hctx, plan, B, L, acc, on_bucket_ready=None):
+    """Backward of seqcls_head_and_loss: score dW / db, final RMSNorm, the B row gradients scattered into a zeroed dx [B*L, d]."""
+    dx_rows = K.seqcls_head_bwd(hctx["dlogits"], hctx["nf"], hctx["x"], hctx["rows"], hctx["rstd"], lm["norm"], lm["score_w"],
+                                grads.get("score_w"), grads.get("score_b"), grads.get("norm"), acc)
+    dx = K.scatter_rows(dx_rows, hctx["rows"], B * L)
+    hctx.clear()
+    if on_bucket_ready is not None:
+        on_bucket_ready("head")
+    return dx
+
+
+def head_backward_of(hctx):
+    """The head backward that matches the head context: lm_head + CE (head_and_loss) or the classification head."""
+    return seqcls_head_backward if hctx.get("seqcls") else head_backward
+
+
 def decoder_backward(K, lm, grads, grads_layers, tc, ctx, hctx, plan, B, L, kmask, kstart=None, qend=None, accumulate=False,
                      on_bucket_ready=None):
-    """Backward of head_and_loss + decoder_forward.  Returns dx [B*L, d], the gradient w.r.t. the merged input embeddings.
-    Fires on_bucket_ready("head") and (("layer", i, "down" | "gu" | "attn")) as each gradient bucket completes."""
+    """Backward of head_and_loss (or seqcls_head_and_loss) + decoder_forward.  Returns dx [B*L, d], the gradient w.r.t. the merged input
+    embeddings.  Fires on_bucket_ready("head") and (("layer", i, "down" | "gu" | "attn")) as each gradient bucket completes."""
     H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
     acc = accumulate
     saved, cos, sin, scale = ctx["saved"], ctx["cos"], ctx["sin"], ctx["scale"]
-    dx = head_backward(K, lm, grads, hctx, plan, B, L, acc, on_bucket_ready)
+    dx = head_backward_of(hctx)(K, lm, grads, hctx, plan, B, L, acc, on_bucket_ready)
     # The weight-gradient GEMMs are off the critical path (nothing in the backward reads a dW): with a side stream (opt-in,
     # hip_ops.side_stream) they queue there, behind the kernel that produced their dY, and their workgroups fill the compute units the
     # dX chain's kernels leave idle in incomplete tile rounds.  The bucket hooks follow them onto that stream (a bucket is ready when

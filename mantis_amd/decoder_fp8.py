@@ -117,7 +117,7 @@ def decoder_backward(K, lm, w8, grads, grads_layers, tc, ctx, hctx, plan, B, L, 
     H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
     acc = accumulate
     saved, cos, sin, scale = ctx["saved"], ctx["cos"], ctx["sin"], ctx["scale"]
-    dx = D.head_backward(K, lm, grads, hctx, plan, B, L, acc, on_bucket_ready)
+    dx = D.head_backward_of(hctx)(K, lm, grads, hctx, plan, B, L, acc, on_bucket_ready)
     rw = w8.rowwise
     # The weight-gradient GEMMs are off the critical path (nothing in the backward reads a dW).  The fp8 GEMM has no K split for the tiles of an
     # incomplete last round (Qwen2-7B: N = 3584 = 14 tiles of 256 -- 448-tile grids = 1.75 rounds on 256 CUs on five of the twelve shapes), so

@@ -727,6 +727,73 @@ def ce_fwd_bwd(logits, targets, V, grad_scale, loss_scale, write_grad=True):
     return loss, count
 
 
+# ----------------------------------------------------------------------------------------------------------- classification head
+SEQCLS_PROBLEM = {"regression": 0, "single_label_classification": 1, "multi_label_classification": 2}
+
+
+def _seqcls_check(rc, what):
+    """The C entries answer a shape outside 1 <= C <= 128, d % 8 == 0, d <= 8192 with the invalid-argument code: a ValueError here."""
+    if rc == -1:
+        raise ValueError(f"{what}: unsupported shape (1 <= num_labels <= 128, hidden size a multiple of 8 up to 8192, B >= 1)")
+    _lib.check(rc, what)
+
+
+def seqcls_pool_index(input_ids, pad_token_id):
+    """input_ids int64 [B, T] on the device -> int32 [B]: (first position of pad_token_id) - 1 mod T, T - 1 without one (or with
+    pad_token_id None).  No host readback."""
+    if input_ids.dtype != torch.int64 or input_ids.dim() != 2 or not input_ids.is_contiguous():
+        raise ValueError(f"input_ids: expected a contiguous int64 [B, T] tensor, got {input_ids.dtype} {tuple(input_ids.shape)}")
+    B, T = input_ids.shape
+    out = torch.empty((B,), dtype=torch.int32, device=input_ids.device)
+    rc = _L.mantis_seqcls_pool_index(_p(input_ids), B, T, 0 if pad_token_id is None else int(pad_token_id), int(pad_token_id is not None),
+                                     _p(out), _stream())
+    _seqcls_check(rc, "seqcls_pool_index")
+    return out
+
+
+def seqcls_head_fwd(x, pool, norm_w, score_w, score_b, labels, problem_type, B, T, eps, grad_scale=1.0, loss_scale=1.0, write_grad=True):
+    """x bf16 [B*T, d] (before the final norm), pool int32 [B].  labels: float32 [B, C] (regression / multi-label), int32 [B]
+    (single-label) or None.  -> dict(logits fp32 [B, C], loss fp32 [1] | None, status int32 [1] | None, dlogits, nf, rstd, rows)."""
+    _chk2d(x, "x")
+    d = x.shape[1]
+    C = score_w.shape[0]
+    if x.shape[0] != B * T or not x.is_contiguous() or pool.dtype != torch.int32 or pool.numel() != B:
+        raise ValueError(f"seqcls_head_fwd: x {tuple(x.shape)} / pool {tuple(pool.shape)} {pool.dtype} do not match B = {B}, T = {T}")
+    pt = 0
+    if labels is not None:
+        pt = SEQCLS_PROBLEM[problem_type]
+        want = (torch.int32, (B,)) if pt == 1 else (torch.float32, (B, C))
+        if labels.dtype != want[0] or tuple(labels.shape) != want[1] or not labels.is_contiguous():
+            raise ValueError(f"seqcls_head_fwd: {problem_type} labels must be {want[0]} {want[1]}, got {labels.dtype} {tuple(labels.shape)}")
+    dev = x.device
+    nf = torch.empty((B, d), dtype=BF16, device=dev)
+    rstd = torch.empty((B,), dtype=torch.float32, device=dev)
+    rows = torch.empty((B,), dtype=torch.int32, device=dev)
+    logits = torch.empty((B, C), dtype=torch.float32, device=dev)
+    grad = labels is not None and write_grad
+    dlogits = torch.empty((B, C), dtype=torch.float32, device=dev) if grad else None
+    ws = torch.empty((2 * B,), dtype=torch.float32, device=dev) if labels is not None else None
+    loss = torch.empty((1,), dtype=torch.float32, device=dev) if labels is not None else None
+    status = torch.empty((1,), dtype=torch.int32, device=dev) if labels is not None else None
+    rc = _L.mantis_seqcls_head_fwd(_p(x), _p(pool), _p(norm_w), _p(score_w), _p(score_b), _p(labels), pt, B, T, d, C, float(eps),
+                                   float(grad_scale), float(loss_scale), int(grad), _p(nf), _p(rstd), _p(rows), _p(logits), _p(dlogits),
+                                   _p(ws), _p(loss), _p(status), _stream())
+    _seqcls_check(rc, "seqcls_head_fwd")
+    return dict(logits=logits, loss=loss, status=status, dlogits=dlogits, nf=nf, rstd=rstd, rows=rows)
+
+
+def seqcls_head_bwd(dlogits, nf, x, rows, rstd, norm_w, score_w, grad_score_w, grad_score_b, grad_norm_w, accumulate):
+    """-> dx_rows bf16 [B, d]; grad_* (each may be None) (+)= the score / final-norm weight gradients."""
+    B, d = nf.shape
+    C = score_w.shape[0]
+    dx_rows = torch.empty((B, d), dtype=BF16, device=x.device)
+    ws = torch.empty((B, d), dtype=torch.float32, device=x.device) if grad_norm_w is not None else None
+    rc = _L.mantis_seqcls_head_bwd(_p(dlogits), _p(nf), _p(x), _p(rows), x.shape[0], _p(rstd), _p(norm_w), _p(score_w), B, d, C,
+                                   _p(grad_score_w), _p(grad_score_b), _p(grad_norm_w), int(accumulate), _p(dx_rows), _p(ws), _stream())
+    _seqcls_check(rc, "seqcls_head_bwd")
+    return dx_rows
+
+
 # ----------------------------------------------------------------------------------------------------------- ViT front end
 def im2col(pixels, patch, kp):
     I, C, H, W = pixels.shape

@@ -36,8 +36,9 @@ class Idefics2CausalLMOutputWithPast:
                                  self.image_hidden_states) if v is not None)[k]
 
 
-def _param_specs(cfg: Idefics2Config):
-    """(name, shape) in ARENA ORDER: [vision tower | connector | embed | text layer 0..n-1 | final norm | lm_head]."""
+def _param_specs(cfg: Idefics2Config, head="lm"):
+    """(name, shape) in ARENA ORDER: [vision tower | connector | embed | text layer 0..n-1 | final norm | head]; head = "lm":
+    lm_head.weight (V, d); "seqcls": score.weight (C, d), score.bias (C,) and no lm_head."""
     vc, pc, tc = cfg.vision_config, cfg.perceiver_config, cfg.text_config
     dv, iv, P, C = vc.hidden_size, vc.intermediate_size, vc.patch_size, vc.num_channels
     s = []
@@ -74,7 +75,11 @@ def _param_specs(cfg: Idefics2Config):
               (p + "self_attn.q_proj.weight", (H * hd, d)), (p + "self_attn.k_proj.weight", (Hkv * hd, d)),
               (p + "self_attn.v_proj.weight", (Hkv * hd, d)), (p + "self_attn.o_proj.weight", (d, H * hd)),
               (p + "mlp.gate_proj.weight", (it, d)), (p + "mlp.up_proj.weight", (it, d)), (p + "mlp.down_proj.weight", (d, it))]
-    s += [(t + "norm.weight", (d,)), ("lm_head.weight", (V, d))]
+    s.append((t + "norm.weight", (d,)))
+    if head == "seqcls":
+        s += [("score.weight", (cfg.num_labels, d)), ("score.bias", (cfg.num_labels,))]
+    else:
+        s.append(("lm_head.weight", (V, d)))
     return s
 
 
@@ -82,13 +87,15 @@ class Idefics2ForConditionalGeneration(ArenaModule):
     config_class = Idefics2Config
     supports_gradient_checkpointing = True       # per decoder layer (decoder.decoder_forward(checkpoint=True)); the frozen tower saves nothing anyway
     frozen_prefixes = ("model.vision_model.",)
+    head_kind = "lm"                             # _param_specs(head=...): what follows the final norm in the arena
+    head_prefixes = ("lm_head",)                 # parameter-name prefixes of the head (the "head" gradient bucket = final norm + these)
 
     def __init__(self, config: Idefics2Config, device=None, dtype=torch.bfloat16, init="normal", seed=0):
         super().__init__()
         self.config = config
         self.image_token_id = config.image_token_id
         self.vocab_size = config.vocab_size
-        self._init_arena(_param_specs(config), device, dtype)
+        self._init_arena(_param_specs(config, self.head_kind), device, dtype)
         self.engine = Idefics2Engine(self)
         self._build_views()
         if init == "normal":
@@ -145,7 +152,13 @@ class Idefics2ForConditionalGeneration(ArenaModule):
                            o=g(p + "self_attn.o_proj.weight"),
                            gu=self._flat(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", 2 * it, d), down=g(p + "mlp.down_proj.weight"),
                            ln1=g(p + "input_layernorm.weight"), ln2=g(p + "post_attention_layernorm.weight")))
-        self.lm = dict(embed=g(t + "embed_tokens.weight"), layers=ll, norm=g(t + "norm.weight"), head=g("lm_head.weight"))
+        self.lm = dict(embed=g(t + "embed_tokens.weight"), layers=ll, norm=g(t + "norm.weight"), **self._head_views(g))
+
+    def _head_views(self, g):
+        return dict(head=g("lm_head.weight"))
+
+    def _head_grad_views(self, gv):
+        return dict(head=gv("lm_head.weight"))
 
     def _build_grad_views(self):
         pc, tc = self.config.perceiver_config, self.config.text_config
@@ -153,7 +166,7 @@ class Idefics2ForConditionalGeneration(ArenaModule):
         d, it, dv = tc.hidden_size, tc.intermediate_size, self.config.vision_config.hidden_size
         H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
         t, c = "model.text_model.", "model.connector."
-        self.grads = dict(head=gv("lm_head.weight"), norm=gv(t + "norm.weight"), embed=gv(t + "embed_tokens.weight"))
+        self.grads = dict(norm=gv(t + "norm.weight"), embed=gv(t + "embed_tokens.weight"), **self._head_grad_views(gv))
         self.grads_layers = []
         for i in range(tc.num_hidden_layers):
             p = f"{t}layers.{i}."
@@ -209,7 +222,7 @@ class Idefics2ForConditionalGeneration(ArenaModule):
         'attn'), then 'front' = connector (modality projection + perceiver) + token embedding."""
         self._ensure_grad_arena()
         span = self._bucket_span
-        out = {"head": span(lambda n: n.startswith("model.text_model.norm") or n.startswith("lm_head"))}
+        out = {"head": span(lambda n: n.startswith("model.text_model.norm") or n.startswith(self.head_prefixes))}
         for i in range(self.config.text_config.num_hidden_layers):
             p = f"model.text_model.layers.{i}."
             out[("layer", i, "down")] = span(lambda n: n == p + "mlp.down_proj.weight")
@@ -249,6 +262,115 @@ class Idefics2ForConditionalGeneration(ArenaModule):
         if not return_dict:
             return ((loss,) if loss is not None else ()) + ((logits,) if logits is not None else ())
         return Idefics2CausalLMOutputWithPast(loss=loss, logits=logits)
+
+
+@dataclass
+class SequenceClassifierOutputWithPast:
+    """transformers.modeling_outputs.SequenceClassifierOutputWithPast, as the reference class returns it (modeling_idefics2.py:2216-2222)"""
+    loss: Optional[torch.Tensor] = None
+    logits: Optional[torch.Tensor] = None
+    past_key_values: Optional[Tuple] = None
+    hidden_states: Optional[Tuple] = None
+    attentions: Optional[Tuple] = None
+
+    def __getitem__(self, k):
+        if isinstance(k, str):
+            return getattr(self, k)
+        return tuple(v for v in (self.loss, self.logits, self.past_key_values, self.hidden_states, self.attentions) if v is not None)[k]
+
+
+class Idefics2ForSequenceClassification(Idefics2ForConditionalGeneration):
+    """Drop-in for the reference fork's `Idefics2ForSequenceClassification` (modeling_idefics2.py:2017-2222; what `train_idefics2.py
+    --problem_type regression | single_label_classification | multi_label_classification` instantiates): the same tower, connector,
+    merger and Mistral decoder as the generation class -- the same engine legs, arena layout and kernels -- ending in
+    `score = nn.Linear(hidden_size, num_labels)` (with bias) on the pooled position of every row instead of lm_head + cross-entropy.
+    Parameter names are the reference's (`score.weight`, `score.bias`, no `lm_head.weight`).  `labels`: float [B, num_labels] for
+    regression / multi-label ([B] or [B, 1] also for num_labels == 1), integer class ids [B] for single-label.  The output's `logits`
+    are the pooled fp32 [B, num_labels].  Refused: packed rows (`segment_ids`), `inputs_embeds`, KV cache, `output_hidden_states`."""
+    head_kind = "seqcls"
+    head_prefixes = ("score.",)
+
+    def __init__(self, config: Idefics2Config, device=None, dtype=torch.bfloat16, init="normal", seed=0):
+        C = config.num_labels
+        if not 1 <= C <= 128:
+            raise ValueError(f"num_labels = {C}: the classification head is built for 1 <= num_labels <= 128")
+        super().__init__(config, device=device, dtype=dtype, init=init, seed=seed)
+        self.num_labels = C
+
+    def _head_views(self, g):
+        return dict(score_w=g("score.weight"), score_b=g("score.bias"))
+
+    def _head_grad_views(self, gv):
+        return dict(score_w=gv("score.weight"), score_b=gv("score.bias"))
+
+    def get_output_embeddings(self):
+        return None
+
+    def resolve_problem_type(self, labels):
+        """config.problem_type, inferred ONCE from num_labels and the label dtype where it is None (modeling_idefics2.py:2192-2198)."""
+        cfg = self.config
+        if cfg.problem_type is None:
+            if self.num_labels == 1:
+                cfg.problem_type = "regression"
+            elif self.num_labels > 1 and labels.dtype in (torch.long, torch.int):
+                cfg.problem_type = "single_label_classification"
+            else:
+                cfg.problem_type = "multi_label_classification"
+        return cfg.problem_type
+
+    def prepare_labels(self, labels, B):
+        """labels as the batch carries them -> (device tensor in the head kernel's layout or None, problem type): float32 [B, C] for
+        regression / multi-label, int32 [B] for single-label.  Wrong dtypes / shapes raise ValueError, class ids outside
+        [0, num_labels) IndexError (on the host where the labels are host tensors, else through the kernel's status word)."""
+        if labels is None:
+            return None, self.config.problem_type
+        labels = torch.as_tensor(labels)
+        C = self.num_labels
+        problem = self.resolve_problem_type(labels)
+        if problem == "single_label_classification":
+            if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+                raise ValueError(f"single_label_classification takes integer class labels [B], got {labels.dtype}")
+            if labels.numel() != B:
+                raise ValueError(f"single_label_classification takes one class label per sample ([{B}]), got {tuple(labels.shape)}")
+            if labels.device.type == "cpu" and bool(((labels < 0) | (labels >= C)).any()):
+                raise IndexError(f"class label(s) outside [0, num_labels = {C}) (torch.nn.CrossEntropyLoss: 'Target out of bounds')")
+            return labels.reshape(B).to(self.device, non_blocking=True).to(torch.int32).contiguous(), problem
+        if not labels.dtype.is_floating_point:
+            raise ValueError(f"{problem} takes floating-point labels [B, num_labels], got {labels.dtype}")
+        ok = tuple(labels.shape) == (B, C) or (C == 1 and tuple(labels.shape) in ((B,), (B, 1)))
+        if not ok:
+            raise ValueError(f"{problem} takes labels of shape [{B}, {C}], got {tuple(labels.shape)}")
+        return labels.reshape(B, C).to(self.device, non_blocking=True).to(torch.float32).contiguous(), problem
+
+    # ------------------------------------------------------------------ forward (modeling_idefics2.py:2080-2222)
+    def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None, pixel_values=None,
+                pixel_attention_mask=None, image_hidden_states=None, labels=None, use_cache=None, output_attentions=None,
+                output_hidden_states=None, return_dict=None, _record=None):
+        if inputs_embeds is not None or past_key_values is not None or use_cache or image_hidden_states is not None:
+            raise NotImplementedError("inputs_embeds / KV cache / precomputed image states are out of scope: training and evaluation "
+                                      "forward from input_ids only")
+        if output_attentions or output_hidden_states:
+            raise NotImplementedError("output_attentions / output_hidden_states are not produced by the fused kernels")
+        if position_ids is not None:
+            raise NotImplementedError("explicit position_ids (the reference passes None: Mistral's default arange)")
+        return_dict = return_dict if return_dict is not None else self.config.use_return_dict
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        want_grads = self.training and labels is not None and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if want_grads:
+            loss = self._autograd_step(lambda: self.engine.step(
+                input_ids, attention_mask, labels, pixel_values, pixel_attention_mask, grad_scale=1.0, loss_scale=1.0, compute_grads=True,
+                overwrite_grads=True, record=_record))
+            logits = self._last_logits
+        else:
+            # evaluation (Trainer.evaluate / prediction_step under no_grad): the same pooled logits and loss, no backward
+            out = self.engine.step(input_ids, attention_mask, labels, pixel_values, pixel_attention_mask, compute_grads=False,
+                                   record=_record)
+            loss = None if labels is None else out["loss"].reshape(())
+            logits = out["logits"]
+        if not return_dict:
+            return ((loss,) if loss is not None else ()) + (logits,)
+        return SequenceClassifierOutputWithPast(loss=loss, logits=logits)
 
 
 class Idefics2Engine:
@@ -472,7 +594,17 @@ class Idefics2Engine:
         am_cpu = attention_mask.detach().to("cpu") if attention_mask.device.type != "cpu" else attention_mask
         ids_d = input_ids.to(dev, non_blocking=True)
         attn_d = attention_mask.to(dev, non_blocking=True).to(torch.int64)
-        lab_d = None if labels is None else labels.to(dev, non_blocking=True).to(torch.int64)
+        seqcls = m.head_kind == "seqcls"          # classification head: `labels` are per-sample targets, not token ids
+        if seqcls:
+            if segment_ids is not None:
+                raise NotImplementedError("packed rows (segment_ids) have no pooled position: the classification head takes one sample "
+                                          "per row")
+            if cfg.pad_token_id is None and B != 1:
+                raise ValueError("Cannot handle batch sizes > 1 if no padding token is defined.")
+            cls_labels, problem = m.prepare_labels(labels, B)
+            if compute_grads and cls_labels is None:
+                raise ValueError("a training step of the classification head needs labels")
+        lab_d = None if labels is None or seqcls else labels.to(dev, non_blocking=True).to(torch.int64)
         img = cctx = None
         n_rows = 0
         is_img = ids_cpu == IMG
@@ -513,21 +645,33 @@ class Idefics2Engine:
             K.pack_segments(plan, ids_d, seg_d, -(2 ** 62))
             kstart, qend = plan.kstart, plan.qend
             plan.position_ids = (torch.arange(T, device=dev, dtype=torch.int64)[None] - kstart.to(torch.int64)).contiguous()
-        D.compact_ce_rows(plan, ids_cpu, am_cpu, labels, IMG, IMG, dev, vocab_size=tc.vocab_size,      # labels equal to image_token_id are
-                          refuse_image_targets=True)                                                  # the ignored ones
+        if not seqcls:
+            D.compact_ce_rows(plan, ids_cpu, am_cpu, labels, IMG, IMG, dev, vocab_size=tc.vocab_size,      # labels equal to image_token_id
+                              refuse_image_targets=True)                                                  # are the ignored ones
         x = K.pack_rows_fwd(plan, ids_d, m.lm["embed"], img)
         if record is not None and img is not None:
             record["merged_embeds"] = x.view(B, T, -1)
         kmask = None if D.no_padding(am_cpu, 0, T) else plan.kmask      # no pad position in the batch: no key mask (host-side decision)
         x, dctx = D8.forward(K, self, m.lm, tc, x, B, T, plan.position_ids, kmask, kstart, compute_grads, record,
                              checkpoint=m.is_gradient_checkpointing)
-        loss, count, logits_full, hctx = D.head_and_loss(K, m.lm, tc, x, plan, B, T, labels is not None, grad_scale, loss_scale,
-                                                         compute_grads, need_logits, record)
-        if count is not None and not self._verified:
-            if int(count[1]) != 0:
-                raise IndexError(f"{int(count[1])} label(s) are >= vocab_size {tc.vocab_size}")
-            self._verified = True
-        out = dict(loss=loss, logits=logits_full, plan=plan)
+        if seqcls:
+            # final norm + score + loss on the B pooled rows (decoder.seqcls_head_and_loss); "logits" are the pooled fp32 [B, C]
+            loss, logits_full, status, hctx, pool = D.seqcls_head_and_loss(
+                K, m.lm, tc, x, ids_d.contiguous(), cfg.pad_token_id, cls_labels, problem, B, T, grad_scale, loss_scale,
+                compute_grads and cls_labels is not None)
+            if status is not None and not self._verified:
+                if int(status[0]) != 0:
+                    raise IndexError(f"{int(status[0])} class label(s) are outside [0, num_labels = {cfg.num_labels})")
+                self._verified = True
+            out = dict(loss=loss, logits=logits_full, plan=plan, pooled_positions=pool)
+        else:
+            loss, count, logits_full, hctx = D.head_and_loss(K, m.lm, tc, x, plan, B, T, labels is not None, grad_scale, loss_scale,
+                                                             compute_grads, need_logits, record)
+            if count is not None and not self._verified:
+                if int(count[1]) != 0:
+                    raise IndexError(f"{int(count[1])} label(s) are >= vocab_size {tc.vocab_size}")
+                self._verified = True
+            out = dict(loss=loss, logits=logits_full, plan=plan)
         if not compute_grads:
             return out
         acc = not overwrite_grads
