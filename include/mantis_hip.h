@@ -345,6 +345,38 @@ int mantis_stream_create_cu_mask(int first_cu, int n_cus, void** stream_out);
 int mantis_stream_create_priority(int level, void** stream_out, int* levels_out);
 int mantis_stream_destroy(void* stream);
 
+/* ---- greedy decoding with a KV cache (csrc/decode.hip).  Replaces the cached branch of HF LlamaAttention.forward (HF:models/llama/
+ * modeling_llama.py, attention with `past_key_values`), the M = batch linears of a decode step and greedy search's argmax, as driven by
+ * /root/reference/mantis/models/mllava/modeling_llava.py:478-508,551-602.  All entries are deterministic (fixed summation orders, no atomics).
+ *
+ * Cache layout (per decoder layer): K and V are each bf16 [B, Hkv, S_max, hd], head-major: the keys of one (sample, kv head) are one
+ * contiguous stream.  Slot s of sample b holds position s of the (merged) sequence, padding slots included; a key is live where
+ * kmask[b, s] != 0 and s < n_keys[b]. */
+/* C[M, N] = epi(A[M, K] . W[N, K]^T), 1 <= M <= 16 (else invalid argument), W as the arena stores it (nn.Linear [out, in]).  Weight-streaming:
+ * one workgroup per 16-row strip of W (N need not be a multiple of 16), 16-byte read-once loads, fp32 accumulation in a fixed order.
+ * epi: + bias[N] (nullable), then -- the product rounded to bf16 first, as mantis_gemm_bf16_nt does -- + residual[M, ldr] (nullable).
+ * K % 8, lda % 8, ldw % 8 == 0 and 16-byte aligned A / W, else the unsupported code. */
+int mantis_linear_skinny_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int M, int N, int K,
+                              const void* bias, const void* residual, int64_t ldr, void* stream);
+/* Rows of a fused q|k|v buffer [R, ld] (q: H heads, then k and v: Hkv heads each) -> the cache: K and V of row r go to slot slot[r] (int32;
+ * negative or >= S_max: skipped) of sample r / rows_per_sample.  cos_tab / sin_tab bf16 [R, hd/2] (both or neither): q is rotated IN PLACE and k
+ * on its way to the cache (the buffer's k columns stay unrotated), with mantis_rope_apply's arithmetic and rounding; NULL: plain copy, q untouched
+ * (prefill: K was rotated by the projection).  hd % 16 == 0. */
+int mantis_kv_cache_write(void* qkv, int64_t ld, void* k_cache, void* v_cache, const int32_t* slot, const void* cos_tab, const void* sin_tab,
+                          int64_t R, int rows_per_sample, int H, int Hkv, int hd, int S_max, void* stream);
+/* O[b, h] = softmax(scale * Q[b, h] . K[b, kv(h)]^T + mask) . V[b, kv(h)] over slots 0 .. min(n_keys[b], S_max) - 1 (n_keys int32 [B]) with
+ * kmask int32 [B, S_max] (nullable, 1 = live).  Q, O: [B, ld] rows, head h at column h * hd.  grid = splits x Hkv x B: the H / Hkv (<= 8) query
+ * heads of a kv head share a workgroup, K / V are read once per kv head.  splits = mantis_attn_decode_splits(B, Hkv, S_max), a pure function of
+ * its arguments and the device's CU count; split i covers slots [i * chunk, (i + 1) * chunk), chunk = ceil(S_max / splits) rounded up to 64.
+ * The fp32 partials (m, l, o) of every split go through `workspace` (mantis_attn_decode_workspace_bytes) and are combined in split order.
+ * A row without a live key gives zeros.  hd in {16, 64, 128}, else the unsupported code. */
+int mantis_attn_decode(const void* Q, int64_t ldq, const void* k_cache, const void* v_cache, const int32_t* kmask, const int32_t* n_keys,
+                       void* O, int64_t ldo, void* workspace, int B, int H, int Hkv, int hd, int S_max, float scale, void* stream);
+int mantis_attn_decode_splits(int B, int Hkv, int S_max);                       /* returns the split count */
+int mantis_attn_decode_workspace_bytes(int B, int H, int Hkv, int hd, int S_max);   /* returns bytes */
+/* out[b] (int64) = index of the maximum of logits[b, 0 .. V) (bf16, row stride ld); ties resolve to the LOWEST index; NaN-free input assumed. */
+int mantis_argmax_rows(const void* logits, int64_t ld, int B, int V, int64_t* out, void* stream);
+
 int mantis_version(void);
 
 #ifdef __cplusplus

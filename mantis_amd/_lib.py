@@ -81,6 +81,12 @@ SIGNATURES = {
     "mantis_stream_create_cu_mask": [I, I, P],
     "mantis_stream_create_priority": [I, P, P],
     "mantis_stream_destroy": [P],
+    "mantis_linear_skinny_bf16": [P, L, P, L, P, L, I, I, I, P, P, L, P],
+    "mantis_kv_cache_write": [P, L, P, P, P, P, P, L, I, I, I, I, I, P],
+    "mantis_attn_decode": [P, L, P, P, P, P, P, L, P, I, I, I, I, I, F, P],
+    "mantis_attn_decode_splits": [I, I, I],
+    "mantis_attn_decode_workspace_bytes": [I, I, I, I, I],
+    "mantis_argmax_rows": [P, L, I, I, P, P],
     "mantis_version": [],
 }
 

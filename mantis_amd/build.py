@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libmantis_hip.so")
-SOURCES = ["pack", "norm", "act", "rope", "ce", "seqcls", "vit","gemm", "gemm176", "gemm_fp8", "attn", "attn_fwd64", "optim"]
+SOURCES = ["pack", "norm", "act", "rope", "ce", "seqcls", "vit","gemm", "gemm176", "gemm_fp8", "attn", "attn_fwd64", "optim", "decode"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast"]
 # attn_fwd64: the hand-placed instruction stream wants one VALU instruction per source operation (no v_pk_* packing of f32 pairs)
 EXTRA_FLAGS = {"attn_fwd64": ["-fno-slp-vectorize"]}

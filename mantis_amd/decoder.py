@@ -45,13 +45,16 @@ def layer_forward(K, lw, tc, x, B, L, cos, sin, kmask, kstart, scale):
     return x_out, (x, rstd1, qkv, o, lse, x_mid, rstd2, gu, n1, n2, a)
 
 
-def decoder_forward(K, lm, tc, x, B, L, position_ids, kmask, kstart=None, compute_grads=True, record=None, rope=None, checkpoint=False):
+def decoder_forward(K, lm, tc, x, B, L, position_ids, kmask, kstart=None, compute_grads=True, record=None, rope=None, checkpoint=False,
+                    kv_sink=None):
     """x [B*L, d] merged input embeddings -> (hidden states before the final norm, ctx for decoder_backward).
     `rope` = (cos, sin) tables [B*L, hd/2] built by the caller (Qwen2-VL's multimodal RoPE); default: 1-D RoPE of position_ids.
     A layer dict may carry `qkv_b`, the fused q|k|v bias (Qwen2: HF:models/qwen2_vl/modeling_qwen2_vl.py:501-503).
     checkpoint: activation checkpointing per decoder layer (`--gradient_checkpointing True`,
     /root/reference/mantis/train/scripts/train_mllava.sh:168; HF wraps every LlamaDecoderLayer in torch.utils.checkpoint,
-    transformers/models/llama/modeling_llama.py:284-325): keep only each layer's INPUT and run the layer's forward again in the backward."""
+    transformers/models/llama/modeling_llama.py:284-325): keep only each layer's INPUT and run the layer's forward again in the backward.
+    kv_sink (prefill of generation.py; default None leaves this loop as it is): called as kv_sink(i, qkv) with layer i's fused q|k|v
+    (q and k rotated) before the buffer is dropped."""
     hd = tc.head_dim
     scale = hd ** -0.5
     cos, sin = rope if rope is not None else K.rope_table(position_ids.reshape(-1), inv_freq(hd, tc.rope_theta).to(x.device))
@@ -62,11 +65,46 @@ def decoder_forward(K, lm, tc, x, B, L, position_ids, kmask, kstart=None, comput
             # 288 GB of HBM: by default keep the cheap-to-recompute tensors too (n1, n2, a: +370 MB per layer) instead of re-running
             # RMSNorm / SwiGLU in the backward; with `checkpoint` only the layer input stays
             saved.append((x,) if checkpoint else keep)
+        if kv_sink is not None:
+            kv_sink(i, keep[2])
         del keep
         x = x_out
         if record is not None:
             record[f"llm_layer{i}_out"] = x.view(B, L, -1)
     return x, dict(saved=saved, cos=cos, sin=sin, scale=scale)
+
+
+def layer_decode(K, lw, tc, x, cache_k, cache_v, slot, cos, sin, kmask, n_keys, scale, ws=None):
+    """One decoder block for ONE new token per sample against the KV cache: x [B, d] -> x_out [B, d].  The cached branch of HF
+    LlamaDecoderLayer / LlamaAttention.forward (transformers/models/llama/modeling_llama.py, `past_key_values`): the new key (rotated at
+    the token's position: cos / sin [B, hd/2]) and value go to cache slot slot[b]; the query attends slots 0 .. n_keys[b] - 1 where kmask is
+    live (the new token's own slot included).  Same operator order as layer_forward, on the weight-streaming kernels."""
+    H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
+    eps = tc.rms_norm_eps
+    n1, _ = K.rmsnorm_fwd(x, lw["ln1"], eps, want_rstd=False)
+    qkv = K.linear_decode(n1, lw["qkv"], bias=lw.get("qkv_b"))
+    K.kv_cache_write(qkv, cache_k, cache_v, slot, cos, sin, 1, H, Hkv, hd)            # RoPE on q (in place) and k, then append
+    o = K.attn_decode(qkv, cache_k, cache_v, kmask, n_keys, H, Hkv, hd, scale, ws=ws)
+    x_mid = K.linear_decode(o, lw["o"], residual=x)
+    n2, _ = K.rmsnorm_fwd(x_mid, lw["ln2"], eps, want_rstd=False)
+    a = K.swiglu_fwd(K.linear_decode(n2, lw["gu"]))
+    return K.linear_decode(a, lw["down"], residual=x_mid)
+
+
+def decoder_decode(K, lm, tc, x, caches, slot, position, kmask, n_keys, ws=None):
+    """All decoder blocks for one new token per sample: x [B, d] embeddings -> hidden states before the final norm.  caches: per layer
+    (K, V); position int64 [B]: the token's RoPE position (the reference's `attention_mask.sum(1) - 1`, modeling_llava.py:508)."""
+    hd = tc.head_dim
+    cos, sin = K.rope_table(position.reshape(-1), inv_freq(hd, tc.rope_theta).to(x.device))
+    for i in range(tc.num_hidden_layers):
+        x = layer_decode(K, lm["layers"][i], tc, x, caches[i][0], caches[i][1], slot, cos, sin, kmask, n_keys, hd ** -0.5, ws=ws)
+    return x
+
+
+def head_rows(K, lm, tc, x):
+    """Final norm + lm_head on the given rows x [M, d] (one per sample: generation never forms [B, L, V]) -> bf16 logits [M, pad8(V)]"""
+    nf, _ = K.rmsnorm_fwd(x, lm["norm"], tc.rms_norm_eps, want_rstd=False)
+    return K.linear_decode(nf, lm["head"], ldc=K.pad8(tc.vocab_size))
 
 
 def no_padding(attention_mask_cpu, grown, L):

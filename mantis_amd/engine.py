@@ -153,7 +153,7 @@ class LlavaEngine:
 
     # ------------------------------------------------------------------------------------------------ full step
     def step(self, input_ids, attention_mask, labels, pixel_values, grad_scale=1.0, loss_scale=1.0, compute_grads=True,
-             overwrite_grads=True, need_logits=False, record=None, on_bucket_ready=None, segment_ids=None):
+             overwrite_grads=True, need_logits=False, record=None, on_bucket_ready=None, segment_ids=None, kv_sink=None):
         """One forward (+ backward).  Returns dict(loss=fp32[1] on device, logits=[B,L,V] or None, plan=...).
 
         segment_ids (int [B,T], optional): sample packing (/root/reference/mantis/train/data.py:1546-1671) -- several samples in
@@ -161,7 +161,9 @@ class LlavaEngine:
         consumed by the attention kernels), position ids restart per sample, no token is predicted across a sample boundary.
 
         grad_scale multiplies d(loss) (1/GA for Trainer.training_step); loss_scale multiplies the returned loss.
-        overwrite_grads: first micro-batch after zero_grad -> gradient kernels overwrite instead of accumulate."""
+        overwrite_grads: first micro-batch after zero_grad -> gradient kernels overwrite instead of accumulate.
+        kv_sink (generation.prefill, with compute_grads=False): receives every decoder layer's fused q|k|v (decoder.decoder_forward); the step
+        then stops before the head and returns dict(hidden=[B*L, d] before the final norm, plan=..., L=...)."""
         m, cfg, tc = self.m, self.cfg, self.cfg.text_config
         dev = m.device
         ids_cpu = input_ids.detach().to("cpu") if input_ids.device.type != "cpu" else input_ids
@@ -239,6 +241,11 @@ class LlavaEngine:
         # a batch without a single pad position needs no key mask (decided on the host copy of the batch: no device sync): the attention
         # kernels then skip the per-tile mask words altogether
         kmask = None if D.no_padding(am_cpu, grown, L) else plan.kmask
+        if kv_sink is not None:
+            if compute_grads or labels is not None:
+                raise ValueError("kv_sink is the prefill of generation: compute_grads=False, no labels")
+            x, _ = D8.forward(K, self, m.lm, tc, x, B, L, plan.position_ids, kmask, kstart, False, record, kv_sink=kv_sink)
+            return dict(hidden=x, plan=plan, L=L)
         x, dctx = D8.forward(K, self, m.lm, tc, x, B, L, plan.position_ids, kmask, kstart, compute_grads, record,
                              checkpoint=m.is_gradient_checkpointing)
         loss, count, logits_full, hctx = D.head_and_loss(K, m.lm, tc, x, plan, B, L, labels is not None, grad_scale, loss_scale,

@@ -636,6 +636,107 @@ def attn_bwd(qkv, o, do, lse, B, Lseq, H, Hkv, hd, kmask, scale, causal, kstart=
     return dqkv
 
 
+# ----------------------------------------------------------------------------------------------------------- decoding with a KV cache
+SKINNY_MAX_ROWS = 16
+SKINNY_MAX_N = 16384         # from this many weight rows on the tiled GEMM was faster at M <= 16 (profiles/generation_decode.md: warm table, provisional)
+
+
+def linear_skinny(x, w, bias=None, residual=None, n_valid=None, ldc=None, out=None):
+    """out[M, N] = epi(x[M, K] . w[N, K]^T) for 1 <= M <= 16 on the weight-streaming kernel (csrc/decode.hip); epi = + bias, + residual.
+    n_valid: use only the first rows of w; ldc > N: padded row stride of a new output."""
+    _chk2d(x, "x"), _chk2d(w, "w")
+    M, K = x.shape
+    N = w.shape[0] if n_valid is None else n_valid
+    if out is None:
+        out = torch.empty((M, N if ldc is None else ldc), dtype=BF16, device=x.device)
+    else:
+        _chk2d(out, "out")
+    prof = _launch().timer
+    if prof is not None:
+        e0 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+    rc = _L.mantis_linear_skinny_bf16(_p(x), x.stride(0), _p(w), w.stride(0), _p(out), out.stride(0), M, N, K, _p(bias), _p(residual),
+                                      0 if residual is None else residual.stride(0), _stream())
+    _lib.check(rc, f"linear_skinny M={M} N={N} K={K}")
+    if prof is not None:
+        e1 = torch.cuda.Event(enable_timing=True)
+        e1.record()
+        prof.append(("linear_skinny_kernel", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N * (1 + (residual is not None))), e0, e1))
+    return out
+
+
+def decode_uses_skinny(M, N):
+    return M <= SKINNY_MAX_ROWS and N < SKINNY_MAX_N
+
+
+def linear_decode(x, w, bias=None, residual=None, n_valid=None, ldc=None):
+    """The linear of a decode step: the weight-streaming kernel up to 16 rows and under 16384 weight rows, the tiled GEMM elsewhere (a pure
+    function of the shape; profiles/generation_decode.md holds the table this choice was fitted on: at the 8B geometry q|k|v, o and down take
+    the skinny kernel, gate|up and lm_head the GEMM)."""
+    if decode_uses_skinny(x.shape[0], w.shape[0] if n_valid is None else n_valid):
+        return linear_skinny(x, w, bias=bias, residual=residual, n_valid=n_valid, ldc=ldc)
+    return gemm_nt(x, w, bias=bias, residual=residual, n_valid=n_valid, ldc=ldc)
+
+
+def kv_cache_alloc(B, Hkv, S_max, hd, device):
+    """(K, V) of one decoder layer: bf16 [B, Hkv, S_max, hd] each (include/mantis_hip.h: head-major, one stream per (sample, kv head))."""
+    return (torch.zeros((B, Hkv, S_max, hd), dtype=BF16, device=device), torch.zeros((B, Hkv, S_max, hd), dtype=BF16, device=device))
+
+
+def kv_cache_write(qkv, k_cache, v_cache, slot, cos, sin, rows_per_sample, H, Hkv, hd):
+    """K / V of row r of the fused q|k|v buffer -> slot[r] (int32) of sample r // rows_per_sample; with cos / sin [R, hd/2] q is rotated in
+    place and k on its way to the cache."""
+    _chk2d(qkv, "qkv")
+    B, _, S_max, _ = k_cache.shape
+    if slot.dtype != torch.int32 or slot.numel() != qkv.shape[0] or qkv.shape[0] != B * rows_per_sample:
+        raise ValueError(f"kv_cache_write: slot {slot.dtype} {tuple(slot.shape)} for qkv {tuple(qkv.shape)}, B={B}, rows_per_sample={rows_per_sample}")
+    if k_cache.shape != (B, Hkv, S_max, hd) or v_cache.shape != k_cache.shape or not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("kv_cache_write: caches must be contiguous [B, Hkv, S_max, hd]")
+    if qkv.shape[1] < (H + 2 * Hkv) * hd or (cos is not None and (cos.shape != (qkv.shape[0], hd // 2) or not cos.is_contiguous()
+                                                                 or sin.shape != cos.shape or not sin.is_contiguous())):
+        raise ValueError("kv_cache_write: qkv narrower than (H + 2 Hkv) * hd, or cos / sin not contiguous [R, hd/2]")
+    rc = _L.mantis_kv_cache_write(_p(qkv), qkv.stride(0), _p(k_cache), _p(v_cache), _p(slot), _p(cos), _p(sin), qkv.shape[0], rows_per_sample,
+                                  H, Hkv, hd, S_max, _stream())
+    _lib.check(rc, f"kv_cache_write hd={hd}")
+
+
+def attn_decode_splits(B, Hkv, S_max):
+    """(splits, chunk): split i of mantis_attn_decode covers cache slots [i * chunk, (i + 1) * chunk)"""
+    s = _L.mantis_attn_decode_splits(B, Hkv, S_max)
+    return s, ((S_max + s - 1) // s + 63) // 64 * 64
+
+
+def attn_decode_workspace(B, H, Hkv, hd, S_max, device):
+    return torch.empty(max(4, _L.mantis_attn_decode_workspace_bytes(B, H, Hkv, hd, S_max)) // 4, dtype=torch.float32, device=device)
+
+
+def attn_decode(q, k_cache, v_cache, kmask, n_keys, H, Hkv, hd, scale, ws=None):
+    """One query row per (sample, head): q [B, >= H*hd] over the cache slots 0 .. n_keys[b] - 1 (n_keys int32 [B]) with kmask int32
+    [B, S_max] or None.  Returns o [B, H*hd]."""
+    _chk2d(q, "q")
+    B, _, S_max, _ = k_cache.shape
+    if q.shape[0] != B or n_keys.dtype != torch.int32 or n_keys.numel() != B or (kmask is not None and (
+            kmask.dtype != torch.int32 or kmask.shape != (B, S_max) or not kmask.is_contiguous())):
+        raise ValueError("attn_decode: q rows / n_keys int32 [B] / kmask contiguous int32 [B, S_max] do not match the cache")
+    if k_cache.shape != (B, Hkv, S_max, hd) or v_cache.shape != k_cache.shape or not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("attn_decode: caches must be contiguous [B, Hkv, S_max, hd]")
+    if ws is None:
+        ws = attn_decode_workspace(B, H, Hkv, hd, S_max, q.device)
+    o = torch.empty((B, H * hd), dtype=BF16, device=q.device)
+    rc = _L.mantis_attn_decode(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(kmask), _p(n_keys), _p(o), o.stride(0), _p(ws), B, H, Hkv, hd,
+                               S_max, float(scale), _stream())
+    _lib.check(rc, f"attn_decode hd={hd} H/Hkv={H // Hkv}")
+    return o
+
+
+def argmax_rows(logits, V):
+    """int64 [B]: index of the maximum of the first V columns of every row; ties resolve to the lowest index."""
+    _chk2d(logits, "logits")
+    out = torch.empty((logits.shape[0],), dtype=torch.int64, device=logits.device)
+    _lib.check(_L.mantis_argmax_rows(_p(logits), logits.stride(0), logits.shape[0], V, _p(out), _stream()), "argmax_rows")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------------------- packing / loss
 class PackPlan:
     __slots__ = ("B", "T", "L", "N", "I", "src", "attention_mask", "labels", "position_ids", "kmask", "text_pos", "img_slot",

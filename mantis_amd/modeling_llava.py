@@ -223,13 +223,27 @@ class LlavaForConditionalGeneration(ArenaModule):
         out["front"] = span(lambda n: n.startswith("multi_modal_projector.") or n.startswith("language_model.model.embed_tokens"))
         return {k: v for k, v in out.items() if v is not None}
 
+    # ------------------------------------------------------------------ generation (greedy, KV cache: mantis_amd/generation.py)
+    def generate(self, input_ids=None, pixel_values=None, attention_mask=None, max_new_tokens=None, max_length=None, eos_token_id=None,
+                 pad_token_id=None, do_sample=False, num_beams=1, streamer=None, **rest):
+        """Greedy search exactly as HF's `generate` returns it for the reference class (what `chat_mllava` / `chat_mllava_stream` call,
+        /root/reference/mantis/models/mllava/utils.py:33-42,77-88): LongTensor [B, T + n] = the prompt followed by the new tokens, a
+        finished row filled with pad_token_id, stopping when every row has emitted an EOS (int or list) or at the length limit.
+        pixel_values: a tensor or the reference's list of per-sample tensors (None: text only).  B > 1 needs left padding.  Any other
+        generation argument raises NotImplementedError naming it.  Works in train() and eval() mode; touches no gradient buffer."""
+        from . import generation as _generation
+        return _generation.generate(self, input_ids, pixel_values=pixel_values, attention_mask=attention_mask,
+                                    max_new_tokens=max_new_tokens, max_length=max_length, eos_token_id=eos_token_id,
+                                    pad_token_id=pad_token_id, streamer=streamer, do_sample=do_sample, num_beams=num_beams, **rest)
+
     # ------------------------------------------------------------------ forward (contract 2 of SURVEY.md section 8b)
     def forward(self, input_ids=None, pixel_values=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, vision_feature_layer=None, vision_feature_select_strategy=None, labels=None,
                 use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None, return_logits=None,
                 _record=None, segment_ids=None):
         if inputs_embeds is not None or past_key_values is not None or use_cache:
-            raise NotImplementedError("generation / KV-cache paths are out of scope (SURVEY.md section 2); training forward only")
+            raise NotImplementedError("forward() takes no inputs_embeds / past_key_values / use_cache (training and evaluation forward "
+                                      "only); for greedy decoding with a KV cache call generate()")
         if output_attentions or output_hidden_states:
             raise NotImplementedError("output_attentions / output_hidden_states are not produced by the fused kernels")
         if vision_feature_layer is not None and vision_feature_layer != self.config.vision_feature_layer:
