@@ -377,6 +377,12 @@ int mantis_attn_decode_workspace_bytes(int B, int H, int Hkv, int hd, int S_max)
 /* out[b] (int64) = index of the maximum of logits[b, 0 .. V) (bf16, row stride ld); ties resolve to the LOWEST index; NaN-free input assumed. */
 int mantis_argmax_rows(const void* logits, int64_t ld, int B, int V, int64_t* out, void* stream);
 
+/* Idefics3 connector's pixel shuffle (reference: mantis/models/idefics3/modeling_idefics3.py:651-660), a row permutation over the
+ * square H x H patch grid of each of the I images (x: [I*H*H, C] rows of stride ldx; out: [I*(H/s)^2, s*s*C] rows of stride ldo):
+ *   out[i][hq*(H/s) + wq][(hr*s + wr)*C + c] = x[i][(hq*s + hr)*H + wq*s + wr][c]
+ * C % 8 != 0, H % s != 0 or strides / pointers off 16 bytes: MANTIS_EUNSUPPORTED.  No backward entry: the tower below it is frozen. */
+int mantis_pixel_shuffle(const void* x, int64_t ldx, void* out, int64_t ldo, int I, int H, int C, int s, void* stream);
+
 int mantis_version(void);
 
 #ifdef __cplusplus

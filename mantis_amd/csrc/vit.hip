@@ -161,6 +161,30 @@ __global__ __launch_bounds__(256) void navit_prepare_kernel(const float* __restr
     if (tid == 0) status[img] = (tab_ok || (nh == 0 && nw == 0 && s_base == 0)) && s_base == nh * nw ? 0 : 1;
 }
 
+// Idefics3 connector's pixel shuffle (space-to-depth over the square patch grid, W = H, scale s), a pure row permutation:
+//   out[i][hq*(W/s) + wq][(hr*s + wr)*C + c] = x[i][(hq*s + hr)*W + wq*s + wr][c]
+// One 16-byte chunk per thread, indexed by the OUTPUT so consecutive lanes write consecutive addresses (an output row is s*s runs of C
+// contiguous input elements); HBM-bound, one pass, nothing staged.
+__global__ void pixel_shuffle_kernel(const bf16_t* __restrict__ x, long ldx, bf16_t* __restrict__ out, long ldo, int I, int H, int C,
+                                     int s) {
+    const int cpr = C >> 3, Wq = H / s, ss = s * s;
+    const unsigned per_img = (unsigned)(H * H) * (unsigned)cpr;       // chunks per image: < 2^31, checked by the entry point
+    const long total = (long)I * per_img;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long img = i / per_img;                                 // the one 64-bit division; the rest is 32-bit
+        unsigned r = (unsigned)(i - img * per_img);
+        const unsigned c = r % cpr;
+        r /= cpr;
+        const unsigned j = r % ss;
+        r /= ss;
+        const unsigned wq = r % Wq, hq = r / Wq;
+        const unsigned hr = j / s, wr = j - hr * s;
+        const long src = img * H * H + (long)((hq * s + hr) * H + wq * s + wr);
+        const long dst = img * Wq * Wq + (long)(hq * Wq + wq);
+        *reinterpret_cast<u32x4*>(out + dst * ldo + (long)j * C + c * 8) = *reinterpret_cast<const u32x4*>(x + src * ldx + c * 8);
+    }
+}
+
 static inline int ew_grid(long n) {
     long g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
@@ -213,6 +237,17 @@ int mantis_drop_cls(const void* in, void* out, int I, int N, int d, void* stream
     if (I == 0) return MANTIS_OK;
     MANTIS_LAUNCH(drop_cls_kernel, dim3(ew_grid((long)I * N * (d / 8))), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)in, (bf16_t*)out, I, N, d);
+    return mantis_check_launch();
+}
+
+int mantis_pixel_shuffle(const void* x, int64_t ldx, void* out, int64_t ldo, int I, int H, int C, int s, void* stream) {
+    if (I < 0 || H <= 0 || C <= 0 || s <= 0 || ldx < C || ldo < (int64_t)s * s * C) return MANTIS_EINVAL;
+    if (C % 8 || H % s || ldx % 8 || ldo % 8 || ((uintptr_t)x & 15) || ((uintptr_t)out & 15)) return MANTIS_EUNSUPPORTED;
+    if ((long)H * H * (C / 8) >= (1L << 31)) return MANTIS_EUNSUPPORTED;          // the kernel indexes inside an image in 32 bits
+    if (I == 0) return MANTIS_OK;
+    const long total = (long)I * H * H * (C / 8);
+    MANTIS_LAUNCH(pixel_shuffle_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (long)ldx,
+                       (bf16_t*)out, (long)ldo, I, H, C, s);
     return mantis_check_launch();
 }
 

@@ -937,6 +937,18 @@ def navit_prepare(pixels, pixel_mask, patch, side, bucket):
     return real, pm, pos, status
 
 
+def pixel_shuffle(x, I, H, s):
+    """Idefics3 connector's pixel shuffle: x [I*H*H, C] (patch rows of I square H x H grids) -> [I*(H/s)^2, s*s*C], contiguous rows that
+    feed gemm_nt directly; out[i, hq*(H/s)+wq, (hr*s+wr)*C + c] = x[i, (hq*s+hr)*H + wq*s+wr, c]."""
+    _chk2d(x, "pixel_shuffle x")
+    C = x.shape[1]
+    if x.shape[0] != I * H * H:
+        raise ValueError(f"pixel_shuffle: {x.shape[0]} rows for {I} grids of {H} x {H}")
+    out = torch.empty((I * (H // max(s, 1)) ** 2, s * s * C), dtype=BF16, device=x.device)
+    _lib.check(_L.mantis_pixel_shuffle(_p(x), x.stride(0), _p(out), out.stride(0), I, H, C, s, _stream()), "pixel_shuffle")
+    return out
+
+
 def drop_cls(x, I, N):
     out = torch.empty((I * N, x.shape[1]), dtype=BF16, device=x.device)
     _lib.check(_L.mantis_drop_cls(_p(x), _p(out), I, N, x.shape[1], _stream()), "drop_cls")

@@ -36,10 +36,8 @@ class Idefics2CausalLMOutputWithPast:
                                  self.image_hidden_states) if v is not None)[k]
 
 
-def _param_specs(cfg: Idefics2Config, head="lm"):
-    """(name, shape) in ARENA ORDER: [vision tower | connector | embed | text layer 0..n-1 | final norm | head]; head = "lm":
-    lm_head.weight (V, d); "seqcls": score.weight (C, d), score.bias (C,) and no lm_head."""
-    vc, pc, tc = cfg.vision_config, cfg.perceiver_config, cfg.text_config
+def _vision_specs(vc):
+    """(name, shape) of the NaViT SigLIP tower in arena order (shared with the Idefics3 path: the same tower)"""
     dv, iv, P, C = vc.hidden_size, vc.intermediate_size, vc.patch_size, vc.num_channels
     s = []
     v = "model.vision_model."
@@ -53,8 +51,16 @@ def _param_specs(cfg: Idefics2Config, head="lm"):
               (p + "layer_norm1.weight", (dv,)), (p + "layer_norm1.bias", (dv,)), (p + "layer_norm2.weight", (dv,)), (p + "layer_norm2.bias", (dv,)),
               (p + "mlp.fc1.weight", (iv, dv)), (p + "mlp.fc1.bias", (iv,)), (p + "mlp.fc2.weight", (dv, iv)), (p + "mlp.fc2.bias", (dv,))]
     s += [(v + "post_layernorm.weight", (dv,)), (v + "post_layernorm.bias", (dv,))]
-    d, it, V = tc.hidden_size, tc.intermediate_size, tc.vocab_size
-    H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
+    return s
+
+
+def _param_specs(cfg: Idefics2Config, head="lm"):
+    """(name, shape) in ARENA ORDER: [vision tower | connector | embed | text layer 0..n-1 | final norm | head]; head = "lm":
+    lm_head.weight (V, d); "seqcls": score.weight (C, d), score.bias (C,) and no lm_head."""
+    vc, pc, tc = cfg.vision_config, cfg.perceiver_config, cfg.text_config
+    dv = vc.hidden_size
+    s = _vision_specs(vc)
+    d, it = tc.hidden_size, tc.intermediate_size
     c = "model.connector."
     s += [(c + "modality_projection.gate_proj.weight", (it, dv)), (c + "modality_projection.up_proj.weight", (it, dv)),
           (c + "modality_projection.down_proj.weight", (d, it)), (c + "perceiver_resampler.latents", (pc.resampler_n_latents, d))]
@@ -66,6 +72,15 @@ def _param_specs(cfg: Idefics2Config, head="lm"):
               (p + "self_attn.v_proj.weight", (pkv * phd, d)), (p + "self_attn.o_proj.weight", (d, ph * phd)),
               (p + "mlp.gate_proj.weight", (4 * d, d)), (p + "mlp.up_proj.weight", (4 * d, d)), (p + "mlp.down_proj.weight", (d, 4 * d))]
     s += [(c + "perceiver_resampler.norm.weight", (d,))]
+    return s + _text_specs(cfg, head)
+
+
+def _text_specs(cfg, head="lm"):
+    """(name, shape) of [embed | text layer 0..n-1 | final norm | head] in arena order"""
+    tc = cfg.text_config
+    d, it, V = tc.hidden_size, tc.intermediate_size, tc.vocab_size
+    H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
+    s = []
     t = "model.text_model."
     s.append((t + "embed_tokens.weight", (V, d)))
     for i in range(tc.num_hidden_layers):
@@ -89,22 +104,34 @@ class Idefics2ForConditionalGeneration(ArenaModule):
     frozen_prefixes = ("model.vision_model.",)
     head_kind = "lm"                             # _param_specs(head=...): what follows the final norm in the arena
     head_prefixes = ("lm_head",)                 # parameter-name prefixes of the head (the "head" gradient bucket = final norm + these)
+    output_class = Idefics2CausalLMOutputWithPast
 
     def __init__(self, config: Idefics2Config, device=None, dtype=torch.bfloat16, init="normal", seed=0):
         super().__init__()
         self.config = config
         self.image_token_id = config.image_token_id
         self.vocab_size = config.vocab_size
-        self._init_arena(_param_specs(config, self.head_kind), device, dtype)
-        self.engine = Idefics2Engine(self)
+        self._init_arena(self._param_specs(config), device, dtype)
+        self.engine = self._make_engine()
         self._build_views()
         if init == "normal":
             self.reset_parameters(seed)
         self.train()
 
+    def _param_specs(self, config):
+        return _param_specs(config, self.head_kind)
+
+    def _make_engine(self):
+        return Idefics2Engine(self)
+
     def _build_views(self):
-        cfg, vc, pc, tc = self.config, self.config.vision_config, self.config.perceiver_config, self.config.text_config
         g = lambda n: self._param(n).data
+        self._build_vision_views(g)
+        self._build_connector_views(g)
+        self._build_text_views(g)
+
+    def _build_vision_views(self, g):
+        vc = self.config.vision_config
         dv, P, C = vc.hidden_size, vc.patch_size, vc.num_channels
         v = "model.vision_model."
         kraw = C * P * P
@@ -129,7 +156,10 @@ class Idefics2ForConditionalGeneration(ArenaModule):
         self.vt = dict(patch_kp=kp, patch_w_padded=patch_w_padded, patch_b=g(v + "embeddings.patch_embedding.bias"),
                        pos=g(v + "embeddings.position_embedding.weight"), layers=layers,
                        post_ln=(g(v + "post_layernorm.weight"), g(v + "post_layernorm.bias")))
-        d, it = tc.hidden_size, tc.intermediate_size
+
+    def _build_connector_views(self, g):
+        vc, pc, tc = self.config.vision_config, self.config.perceiver_config, self.config.text_config
+        dv, d, it = vc.hidden_size, tc.hidden_size, tc.intermediate_size
         c = "model.connector."
         ph, pkv, phd = pc.resampler_n_heads, pc.num_key_value_heads, pc.resampler_head_dim
         pl = []
@@ -143,6 +173,10 @@ class Idefics2ForConditionalGeneration(ArenaModule):
         self.conn = dict(mp_gu=self._flat(c + "modality_projection.gate_proj.weight", c + "modality_projection.up_proj.weight", 2 * it, dv),
                          mp_down=g(c + "modality_projection.down_proj.weight"), latents=g(c + "perceiver_resampler.latents"),
                          layers=pl, norm=g(c + "perceiver_resampler.norm.weight"))
+
+    def _build_text_views(self, g):
+        tc = self.config.text_config
+        d, it = tc.hidden_size, tc.intermediate_size
         H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
         t = "model.text_model."
         ll = []
@@ -161,11 +195,11 @@ class Idefics2ForConditionalGeneration(ArenaModule):
         return dict(head=gv("lm_head.weight"))
 
     def _build_grad_views(self):
-        pc, tc = self.config.perceiver_config, self.config.text_config
+        tc = self.config.text_config
         gv = self._grad_views.get
-        d, it, dv = tc.hidden_size, tc.intermediate_size, self.config.vision_config.hidden_size
+        d, it = tc.hidden_size, tc.intermediate_size
         H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
-        t, c = "model.text_model.", "model.connector."
+        t = "model.text_model."
         self.grads = dict(norm=gv(t + "norm.weight"), embed=gv(t + "embed_tokens.weight"), **self._head_grad_views(gv))
         self.grads_layers = []
         for i in range(tc.num_hidden_layers):
@@ -174,6 +208,12 @@ class Idefics2ForConditionalGeneration(ArenaModule):
                 qkv=self._gflat(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", (H + 2 * Hkv) * hd, d), o=gv(p + "self_attn.o_proj.weight"),
                 gu=self._gflat(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", 2 * it, d), down=gv(p + "mlp.down_proj.weight"),
                 ln1=gv(p + "input_layernorm.weight"), ln2=gv(p + "post_attention_layernorm.weight")))
+        self._build_connector_grad_views(gv)
+
+    def _build_connector_grad_views(self, gv):
+        pc, tc = self.config.perceiver_config, self.config.text_config
+        d, it, dv = tc.hidden_size, tc.intermediate_size, self.config.vision_config.hidden_size
+        c = "model.connector."
         ph, pkv, phd = pc.resampler_n_heads, pc.num_key_value_heads, pc.resampler_head_dim
         pl = []
         for i in range(pc.resampler_depth):
@@ -261,7 +301,7 @@ class Idefics2ForConditionalGeneration(ArenaModule):
         logits = None if lg is None else lg.float()          # :1882 logits.float()
         if not return_dict:
             return ((loss,) if loss is not None else ()) + ((logits,) if logits is not None else ())
-        return Idefics2CausalLMOutputWithPast(loss=loss, logits=logits)
+        return self.output_class(loss=loss, logits=logits)
 
 
 @dataclass
@@ -380,6 +420,7 @@ class Idefics2Engine:
     def __init__(self, model):
         self.m = model
         self.cfg = model.config
+        self.ignore_index = model.config.image_token_id      # labels equal to image_token_id are the ignored ones (:1898)
         self._verified = False
         self.w8 = None                       # decoder_fp8.Fp8Weights after model.set_precision("fp8")
         self.weights_unchanged = False       # set by MantisHipTrainer on the 2nd.. micro-batch of an accumulation window
@@ -583,6 +624,13 @@ class Idefics2Engine:
         if g["mp_gu"] is not None:
             K.linear_dw(dgu, c["feats"], g["mp_gu"], acc)
 
+    def select_ce_rows(self, plan, ids_cpu, am_cpu, labels, dev):
+        """Shrink the plan's cross-entropy lists to the rows that can carry a label.  Labels equal to image_token_id are the ignored
+        ones on this path (:1898); a target ON an <image> token is refused."""
+        IMG = self.cfg.image_token_id
+        D.compact_ce_rows(plan, ids_cpu, am_cpu, labels, IMG, IMG, dev, vocab_size=self.cfg.text_config.vocab_size,
+                          refuse_image_targets=True)
+
     # ------------------------------------------------------------------ full step
     def step(self, input_ids, attention_mask, labels, pixel_values, pixel_attention_mask=None, grad_scale=1.0, loss_scale=1.0,
              compute_grads=True, overwrite_grads=True, need_logits=False, record=None, on_bucket_ready=None, segment_ids=None):
@@ -623,18 +671,18 @@ class Idefics2Engine:
             if record is not None:
                 record["vision_last_hidden_state"] = feats.view(I, N, -1)
             img, cctx = self.connector_forward(feats, I, N, km_all, record)
-            if record is not None:
-                record["connector_out"] = img.view(I, cfg.perceiver_config.resampler_n_latents, -1)
             n_rows = img.shape[0]
+            if record is not None:
+                record["connector_out"] = img.view(I, n_rows // max(I, 1), -1)
             n_tok = int(is_img.sum())
             if n_tok != n_rows:      # torch raises a shape-mismatch error in inputs_merger (:1564) for this
                 raise ValueError(f"{n_tok} <image> tokens in input_ids but {n_rows} image hidden states "
-                                 f"({I} images x {cfg.perceiver_config.resampler_n_latents} latents)")
+                                 f"({I} images x {n_rows // max(I, 1)} rows)")
             if bool((am_cpu[is_img] == 0).any()):
                 raise NotImplementedError("attention_mask == 0 on an <image> token")
         # inputs_merger (:1545-1565) = the packing plan with ONE slot per <image> token: slot r takes image-hidden row r in row-major
         # order; labels equal to image_token_id are the ignored ones (:1898); positions are Mistral's default arange
-        plan = K.pack_plan(ids_d, attn_d, lab_d, 1, n_rows, IMG if img is not None else -(2 ** 62), -1, IMG, T)
+        plan = K.pack_plan(ids_d, attn_d, lab_d, 1, n_rows, IMG if img is not None else -(2 ** 62), -1, self.ignore_index, T)
         plan.position_ids = torch.arange(T, device=dev, dtype=torch.int64)[None].expand(B, T).contiguous()
         kstart = qend = None
         if segment_ids is not None:
@@ -646,8 +694,7 @@ class Idefics2Engine:
             kstart, qend = plan.kstart, plan.qend
             plan.position_ids = (torch.arange(T, device=dev, dtype=torch.int64)[None] - kstart.to(torch.int64)).contiguous()
         if not seqcls:
-            D.compact_ce_rows(plan, ids_cpu, am_cpu, labels, IMG, IMG, dev, vocab_size=tc.vocab_size,      # labels equal to image_token_id
-                              refuse_image_targets=True)                                                  # are the ignored ones
+            self.select_ce_rows(plan, ids_cpu, am_cpu, labels, dev)
         x = K.pack_rows_fwd(plan, ids_d, m.lm["embed"], img)
         if record is not None and img is not None:
             record["merged_embeds"] = x.view(B, T, -1)
