@@ -108,6 +108,36 @@ class ArenaModule(nn.Module):
         assert b - a == rows * cols, (first, last_incl, b - a, rows, cols)
         return self.arena[a:b].view(rows, cols)
 
+    # ------------------------------------------------------------------ initialisation
+    @torch.no_grad()
+    def reset_parameters(self, seed=0):
+        """HF `_init_weights`: normal(0, initializer_range) wherever `_init_value` does not name a constant.  One generator, parameters in
+        `named_parameters()` order: the drawn values are a function of the seed alone."""
+        std = self.config.text_config.get("initializer_range", 0.02)
+        self._param_version += 1
+        gen = torch.Generator(device=self.device).manual_seed(seed)
+        for name, p in self.named_parameters():
+            value = self._init_value(name, p)
+            if value is not None:
+                p.fill_(value)
+                continue
+            # chunked to bound the fp32 temporary (lm_head is 0.5 G elements)
+            flat = p.view(-1)
+            step = 1 << 26
+            for a in range(0, flat.numel(), step):
+                b = min(flat.numel(), a + step)
+                flat[a:b] = torch.randn(b - a, generator=gen, device=self.device, dtype=torch.float32).mul_(std)
+
+    def _init_value(self, name, p):
+        """The constant `reset_parameters` fills parameter `name` with, or None to draw it: norm weights 1, biases 0, matrices drawn.
+        Classes override this for their own exceptions."""
+        if p.dim() == 1:
+            return 1.0 if ("norm" in name and name.endswith("weight")) else 0.0
+        return None
+
+    def tie_weights(self, *a, **k):
+        return None
+
     @property
     def device(self):
         return self.arena.device
@@ -184,6 +214,33 @@ class ArenaModule(nn.Module):
     def _autograd_step(self, run):
         """loss tensor whose .backward() publishes the gradients of `run()` (see FusedStep); logits, if any, in self._last_logits."""
         return FusedStep.apply(self, self._loss_anchor(), run)
+
+    def _forward_step(self, input_ids, attention_mask, labels, extra, output_class, return_dict, return_logits=None, float_logits=True,
+                      **step_kw):
+        """What every class's `forward()` does once its own refusals are through: `engine.step(input_ids, attention_mask, labels, *extra,
+        **step_kw)` -- fused forward+backward under autograd's eyes when a training loss is asked for, forward only otherwise -- and the
+        (loss, logits) tuple or `output_class`.  return_logits None: training never materialises the [B,L,V] logits unless asked to."""
+        return_dict = return_dict if return_dict is not None else self.config.use_return_dict
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        want_grads = self.training and labels is not None and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if return_logits is None:
+            return_logits = not want_grads
+        if want_grads:
+            # stock `loss.backward()` callers: the fused forward+backward runs now, .backward() publishes the gradients (FusedStep)
+            loss = self._autograd_step(lambda: self.engine.step(
+                input_ids, attention_mask, labels, *extra, grad_scale=1.0, loss_scale=1.0, compute_grads=True, overwrite_grads=True,
+                need_logits=return_logits, **step_kw))
+            logits = self._last_logits
+        else:
+            out = self.engine.step(input_ids, attention_mask, labels, *extra, compute_grads=False, need_logits=return_logits, **step_kw)
+            loss = None if labels is None else out["loss"].reshape(())
+            logits = out["logits"]
+        if float_logits and logits is not None:
+            logits = logits.float()
+        if not return_dict:
+            return ((loss,) if loss is not None else ()) + ((logits,) if logits is not None else ())
+        return output_class(loss=loss, logits=logits)
 
     def _gflat(self, first, last_incl, rows, cols):
         if first not in self._grad_offs:

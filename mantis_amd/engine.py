@@ -16,6 +16,7 @@ import os
 import numpy as np
 import torch
 
+from . import backbone as BB
 from . import decoder as D
 from . import decoder_fp8 as D8
 from . import hip_ops as K   # the ONLY compute backend; tests may monkeypatch `engine.K` with the oracle to test host logic
@@ -54,6 +55,7 @@ class LlavaEngine:
         self._verified = False
         self.w8 = None                       # decoder_fp8.Fp8Weights after model.set_precision("fp8")
         self.weights_unchanged = False       # set by MantisHipTrainer on the 2nd.. micro-batch of an accumulation window
+        self._prefetched = BB.PrefetchSlots()     # towers computed ahead by prefetch_vision: (pixel_values object, feats, N, done event)
 
     def _verify_device_status(self, plan, count):
         st = plan.status.cpu().tolist()
@@ -82,7 +84,7 @@ class LlavaEngine:
         m, vc = self.m, self.cfg.vision_config
         vt = m.vt
         I = pixels.shape[0]
-        P, dv = vc.patch_size, vc.hidden_size
+        P = vc.patch_size
         N = (pixels.shape[2] // P) * (pixels.shape[3] // P)
         patches = K.im2col(pixels, P, vt["patch_kp"])
         pe = K.gemm_nt(patches, vt["patch_w_padded"](), bias=vt["patch_b"])
@@ -91,18 +93,8 @@ class LlavaEngine:
         eps = vc.layer_norm_eps
         if vt["pre_ln"] is not None:
             x = K.layernorm_fwd(x, vt["pre_ln"][0], vt["pre_ln"][1], eps)
-        nh = vc.num_attention_heads
-        hd = dv // nh
         n_layers = vc.num_hidden_layers + self.cfg.vision_feature_layer + 1   # hidden_states[-2] = output of layer N-2
-        for i in range(n_layers):
-            lw = vt["layers"][i]
-            y = K.layernorm_fwd(x, lw["ln1_w"], lw["ln1_b"], eps)
-            qkv = K.gemm_nt(y, lw["qkv_w"], bias=lw["qkv_b"])
-            o, _ = K.attn_fwd(qkv, I, NT, nh, nh, hd, None, hd ** -0.5, False, want_lse=False)
-            x = K.gemm_nt(o, lw["out_w"], bias=lw["out_b"], residual=x)
-            y = K.layernorm_fwd(x, lw["ln2_w"], lw["ln2_b"], eps)
-            hmid = K.gemm_nt(y, lw["fc1_w"], bias=lw["fc1_b"], act=vc.hidden_act)
-            x = K.gemm_nt(hmid, lw["fc2_w"], bias=lw["fc2_b"], residual=x)
+        x = BB.vit_encoder(K, vt["layers"][:n_layers], x, I, NT, vc, None)
         strat = self.cfg.vision_feature_select_strategy
         if strat == "default":          # modeling_llava.py:460-461
             if vt["cls"] is None:
@@ -143,13 +135,7 @@ class LlavaEngine:
             feats, N = self.vision_forward(self._pixels_to_device(pv, dev))
             done = torch.cuda.Event()
             done.record(stream)
-        # one slot per in-flight batch: with the early mode (MantisHipTrainer.prefetch_early) the tower of batch i+1 is enqueued before
-        # step i has picked up its own features
-        if not isinstance(getattr(self, "_prefetched", None), dict):
-            self._prefetched = {}
-        self._prefetched[id(pv)] = (pv, feats, N, done)
-        while len(self._prefetched) > 2:                   # a prefetched batch that never arrives must not pile up
-            self._prefetched.pop(next(iter(self._prefetched)))
+        self._prefetched.put(pv, feats, N, done)
 
     # ------------------------------------------------------------------------------------------------ full step
     def step(self, input_ids, attention_mask, labels, pixel_values, grad_scale=1.0, loss_scale=1.0, compute_grads=True,
@@ -166,7 +152,7 @@ class LlavaEngine:
         then stops before the head and returns dict(hidden=[B*L, d] before the final norm, plan=..., L=...)."""
         m, cfg, tc = self.m, self.cfg, self.cfg.text_config
         dev = m.device
-        ids_cpu = input_ids.detach().to("cpu") if input_ids.device.type != "cpu" else input_ids
+        ids_cpu = BB.to_host(input_ids)
         B, T = ids_cpu.shape
         ign = cfg.ignore_index
         pad_id = cfg.pad_token_id if cfg.pad_token_id is not None else -1
@@ -180,9 +166,8 @@ class LlavaEngine:
         I = 0
         N = 1
         if pixel_values is not None and T != 1:
-            slots = getattr(self, "_prefetched", None)
-            pre = slots.pop(id(pixel_values), None) if isinstance(slots, dict) else None
-            if pre is not None and pre[0] is pixel_values and record is None:
+            pre = self._prefetched.take(pixel_values)
+            if pre is not None and record is None:
                 feats, N = pre[1], pre[2]                       # computed ahead on another stream (prefetch_vision)
                 torch.cuda.current_stream().wait_event(pre[3])
                 feats.record_stream(torch.cuda.current_stream())
@@ -228,7 +213,7 @@ class LlavaEngine:
             img_tok = cfg.image_token_index if (pixel_values is not None and T != 1) else -(2 ** 62)
             K.pack_segments(plan, ids_d, seg_d, img_tok)
             kstart, qend = plan.kstart, plan.qend
-        am_cpu = attention_mask.detach().to("cpu") if attention_mask.device.type != "cpu" else attention_mask
+        am_cpu = BB.to_host(attention_mask)
         D.compact_ce_rows(plan, ids_cpu, am_cpu, labels, cfg.image_token_index if (pixel_values is not None and T != 1) else -(2 ** 62),
                           ign, dev, vocab_size=tc.vocab_size)
         emb_w = m.lm["embed"]

@@ -11,6 +11,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import backbone as BB
 from . import decoder as D
 from . import decoder_fp8 as D8
 from . import hip_ops as K   # tests may monkeypatch `modeling_idefics2.K` with the oracle's operators to test the host logic
@@ -20,7 +21,7 @@ from .configuration_idefics2 import Idefics2Config
 
 
 @dataclass
-class Idefics2CausalLMOutputWithPast:
+class Idefics2CausalLMOutputWithPast(BB.ModelOutput):
     """modeling_idefics2.py:119-152"""
     loss: Optional[torch.Tensor] = None
     logits: Optional[torch.Tensor] = None
@@ -29,27 +30,16 @@ class Idefics2CausalLMOutputWithPast:
     attentions: Optional[Tuple] = None
     image_hidden_states: Optional[torch.Tensor] = None
 
-    def __getitem__(self, k):
-        if isinstance(k, str):
-            return getattr(self, k)
-        return tuple(v for v in (self.loss, self.logits, self.past_key_values, self.hidden_states, self.attentions,
-                                 self.image_hidden_states) if v is not None)[k]
-
 
 def _vision_specs(vc):
     """(name, shape) of the NaViT SigLIP tower in arena order (shared with the Idefics3 path: the same tower)"""
-    dv, iv, P, C = vc.hidden_size, vc.intermediate_size, vc.patch_size, vc.num_channels
+    dv, P, C = vc.hidden_size, vc.patch_size, vc.num_channels
     s = []
     v = "model.vision_model."
     s += [(v + "embeddings.patch_embedding.weight", (dv, C, P, P)), (v + "embeddings.patch_embedding.bias", (dv,)),
           (v + "embeddings.position_embedding.weight", ((vc.image_size // P) ** 2, dv))]
     for i in range(vc.num_hidden_layers):
-        p = f"{v}encoder.layers.{i}."
-        s += [(p + "self_attn.q_proj.weight", (dv, dv)), (p + "self_attn.k_proj.weight", (dv, dv)), (p + "self_attn.v_proj.weight", (dv, dv)),
-              (p + "self_attn.q_proj.bias", (dv,)), (p + "self_attn.k_proj.bias", (dv,)), (p + "self_attn.v_proj.bias", (dv,)),
-              (p + "self_attn.out_proj.weight", (dv, dv)), (p + "self_attn.out_proj.bias", (dv,)),
-              (p + "layer_norm1.weight", (dv,)), (p + "layer_norm1.bias", (dv,)), (p + "layer_norm2.weight", (dv,)), (p + "layer_norm2.bias", (dv,)),
-              (p + "mlp.fc1.weight", (iv, dv)), (p + "mlp.fc1.bias", (iv,)), (p + "mlp.fc2.weight", (dv, iv)), (p + "mlp.fc2.bias", (dv,))]
+        s += BB.vit_layer_specs(f"{v}encoder.layers.{i}.", vc)
     s += [(v + "post_layernorm.weight", (dv,)), (v + "post_layernorm.bias", (dv,))]
     return s
 
@@ -78,18 +68,12 @@ def _param_specs(cfg: Idefics2Config, head="lm"):
 def _text_specs(cfg, head="lm"):
     """(name, shape) of [embed | text layer 0..n-1 | final norm | head] in arena order"""
     tc = cfg.text_config
-    d, it, V = tc.hidden_size, tc.intermediate_size, tc.vocab_size
-    H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
+    d, V = tc.hidden_size, tc.vocab_size
     s = []
     t = "model.text_model."
     s.append((t + "embed_tokens.weight", (V, d)))
     for i in range(tc.num_hidden_layers):
-        p = f"{t}layers.{i}."
-        # same in-layer order as the LLaVA path: [norms | q k v o] [gate up] [down] = reverse of backward completion (DP sub-buckets)
-        s += [(p + "input_layernorm.weight", (d,)), (p + "post_attention_layernorm.weight", (d,)),
-              (p + "self_attn.q_proj.weight", (H * hd, d)), (p + "self_attn.k_proj.weight", (Hkv * hd, d)),
-              (p + "self_attn.v_proj.weight", (Hkv * hd, d)), (p + "self_attn.o_proj.weight", (d, H * hd)),
-              (p + "mlp.gate_proj.weight", (it, d)), (p + "mlp.up_proj.weight", (it, d)), (p + "mlp.down_proj.weight", (d, it))]
+        s += BB.decoder_layer_specs(f"{t}layers.{i}.", tc)      # the same in-layer order on every path
     s.append((t + "norm.weight", (d,)))
     if head == "seqcls":
         s += [("score.weight", (cfg.num_labels, d)), ("score.bias", (cfg.num_labels,))]
@@ -132,29 +116,11 @@ class Idefics2ForConditionalGeneration(ArenaModule):
 
     def _build_vision_views(self, g):
         vc = self.config.vision_config
-        dv, P, C = vc.hidden_size, vc.patch_size, vc.num_channels
         v = "model.vision_model."
-        kraw = C * P * P
-        kp = (kraw + 7) // 8 * 8
-
-        def patch_w_padded():
-            w = g(v + "embeddings.patch_embedding.weight").view(dv, kraw)
-            if kp == kraw:
-                return w
-            out = torch.zeros((dv, kp), dtype=w.dtype, device=w.device)
-            out[:, :kraw] = w
-            return out
-        layers = []
-        for i in range(vc.num_hidden_layers):
-            p = f"{v}encoder.layers.{i}."
-            layers.append(dict(
-                qkv_w=self._flat(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", 3 * dv, dv),
-                qkv_b=self._flat(p + "self_attn.q_proj.bias", p + "self_attn.v_proj.bias", 1, 3 * dv).view(-1),
-                out_w=g(p + "self_attn.out_proj.weight"), out_b=g(p + "self_attn.out_proj.bias"),
-                ln1_w=g(p + "layer_norm1.weight"), ln1_b=g(p + "layer_norm1.bias"), ln2_w=g(p + "layer_norm2.weight"), ln2_b=g(p + "layer_norm2.bias"),
-                fc1_w=g(p + "mlp.fc1.weight"), fc1_b=g(p + "mlp.fc1.bias"), fc2_w=g(p + "mlp.fc2.weight"), fc2_b=g(p + "mlp.fc2.bias")))
+        kp, patch_w_padded = BB.patch_w_padded(self, v + "embeddings.patch_embedding.weight", vc)
         self.vt = dict(patch_kp=kp, patch_w_padded=patch_w_padded, patch_b=g(v + "embeddings.patch_embedding.bias"),
-                       pos=g(v + "embeddings.position_embedding.weight"), layers=layers,
+                       pos=g(v + "embeddings.position_embedding.weight"),
+                       layers=[BB.vit_layer_views(self, f"{v}encoder.layers.{i}.", vc) for i in range(vc.num_hidden_layers)],
                        post_ln=(g(v + "post_layernorm.weight"), g(v + "post_layernorm.bias")))
 
     def _build_connector_views(self, g):
@@ -176,16 +142,8 @@ class Idefics2ForConditionalGeneration(ArenaModule):
 
     def _build_text_views(self, g):
         tc = self.config.text_config
-        d, it = tc.hidden_size, tc.intermediate_size
-        H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
         t = "model.text_model."
-        ll = []
-        for i in range(tc.num_hidden_layers):
-            p = f"{t}layers.{i}."
-            ll.append(dict(qkv=self._flat(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", (H + 2 * Hkv) * hd, d),
-                           o=g(p + "self_attn.o_proj.weight"),
-                           gu=self._flat(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", 2 * it, d), down=g(p + "mlp.down_proj.weight"),
-                           ln1=g(p + "input_layernorm.weight"), ln2=g(p + "post_attention_layernorm.weight")))
+        ll = [BB.decoder_layer_views(f"{t}layers.{i}.", tc, g, self._flat) for i in range(tc.num_hidden_layers)]
         self.lm = dict(embed=g(t + "embed_tokens.weight"), layers=ll, norm=g(t + "norm.weight"), **self._head_views(g))
 
     def _head_views(self, g):
@@ -197,17 +155,9 @@ class Idefics2ForConditionalGeneration(ArenaModule):
     def _build_grad_views(self):
         tc = self.config.text_config
         gv = self._grad_views.get
-        d, it = tc.hidden_size, tc.intermediate_size
-        H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
         t = "model.text_model."
         self.grads = dict(norm=gv(t + "norm.weight"), embed=gv(t + "embed_tokens.weight"), **self._head_grad_views(gv))
-        self.grads_layers = []
-        for i in range(tc.num_hidden_layers):
-            p = f"{t}layers.{i}."
-            self.grads_layers.append(dict(
-                qkv=self._gflat(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", (H + 2 * Hkv) * hd, d), o=gv(p + "self_attn.o_proj.weight"),
-                gu=self._gflat(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", 2 * it, d), down=gv(p + "mlp.down_proj.weight"),
-                ln1=gv(p + "input_layernorm.weight"), ln2=gv(p + "post_attention_layernorm.weight")))
+        self.grads_layers = [BB.decoder_layer_views(f"{t}layers.{i}.", tc, gv, self._gflat) for i in range(tc.num_hidden_layers)]
         self._build_connector_grad_views(gv)
 
     def _build_connector_grad_views(self, gv):
@@ -227,32 +177,15 @@ class Idefics2ForConditionalGeneration(ArenaModule):
                                mp_down=gv(c + "modality_projection.down_proj.weight"), latents=gv(c + "perceiver_resampler.latents"),
                                layers=pl, norm=gv(c + "perceiver_resampler.norm.weight"))
 
-    @torch.no_grad()
-    def reset_parameters(self, seed=0):
-        """normal(0, initializer_range), norm weights 1, biases 0, latents 1 (modeling_idefics2.py:1366-1387, :1275)."""
-        std = self.config.text_config.get("initializer_range", 0.02)
-        self._param_version += 1
-        gen = torch.Generator(device=self.device).manual_seed(seed)
-        for name, p in self.named_parameters():
-            if name.endswith("perceiver_resampler.latents"):
-                p.fill_(1.0)
-            elif p.dim() == 1:
-                p.fill_(1.0 if ("norm" in name and name.endswith("weight")) else 0.0)
-            else:
-                flat = p.view(-1)
-                step = 1 << 26
-                for a in range(0, flat.numel(), step):
-                    b = min(flat.numel(), a + step)
-                    flat[a:b] = torch.randn(b - a, generator=gen, device=self.device, dtype=torch.float32).mul_(std)
+    def _init_value(self, name, p):
+        """modeling_idefics2.py:1366-1387; the perceiver latents start at 1 (:1275)"""
+        return 1.0 if name.endswith("perceiver_resampler.latents") else super()._init_value(name, p)
 
     def get_input_embeddings(self):
         return self.model.text_model.embed_tokens
 
     def get_output_embeddings(self):
         return self.lm_head
-
-    def tie_weights(self, *a, **k):
-        return None
 
     def load_reference_state_dict(self, sd, strict=True):
         return self.copy_state_dict(sd, ignorable=lambda k: k.endswith("position_ids") or ".head." in k, strict=strict)
@@ -262,13 +195,9 @@ class Idefics2ForConditionalGeneration(ArenaModule):
         'attn'), then 'front' = connector (modality projection + perceiver) + token embedding."""
         self._ensure_grad_arena()
         span = self._bucket_span
-        out = {"head": span(lambda n: n.startswith("model.text_model.norm") or n.startswith(self.head_prefixes))}
-        for i in range(self.config.text_config.num_hidden_layers):
-            p = f"model.text_model.layers.{i}."
-            out[("layer", i, "down")] = span(lambda n: n == p + "mlp.down_proj.weight")
-            out[("layer", i, "gu")] = span(lambda n: n in (p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"))
-            out[("layer", i, "attn")] = span(lambda n: n.startswith(p) and ".mlp." not in n)
-        out["front"] = span(lambda n: n.startswith("model.connector.") or n.startswith("model.text_model.embed_tokens"))
+        out = {"head": span(lambda n: n.startswith("model.text_model.norm") or n.startswith(self.head_prefixes)),
+               **BB.decoder_buckets(span, "model.text_model.layers.", self.config.text_config.num_hidden_layers),
+               "front": span(lambda n: n.startswith("model.connector.") or n.startswith("model.text_model.embed_tokens"))}
         return {k: v for k, v in out.items() if v is not None}
 
     # ------------------------------------------------------------------ forward (modeling_idefics2.py:1797-1912)
@@ -281,42 +210,18 @@ class Idefics2ForConditionalGeneration(ArenaModule):
             raise NotImplementedError("output_attentions / output_hidden_states are not produced by the fused kernels")
         if position_ids is not None:
             raise NotImplementedError("explicit position_ids (the reference passes None: Mistral's default arange)")
-        return_dict = return_dict if return_dict is not None else self.config.use_return_dict
-        if attention_mask is None:
-            attention_mask = torch.ones_like(input_ids)
-        want_grads = self.training and labels is not None and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        if return_logits is None:
-            return_logits = not want_grads        # training: the [B,L,V] logits are never materialised unless asked for
-        if want_grads:
-            # stock `loss.backward()` callers: the fused forward+backward runs now, .backward() publishes the gradients (arena.FusedStep)
-            loss = self._autograd_step(lambda: self.engine.step(
-                input_ids, attention_mask, labels, pixel_values, pixel_attention_mask, grad_scale=1.0, loss_scale=1.0, compute_grads=True,
-                overwrite_grads=True, need_logits=return_logits, record=_record))
-            lg = self._last_logits
-        else:
-            out = self.engine.step(input_ids, attention_mask, labels, pixel_values, pixel_attention_mask, compute_grads=False,
-                                   need_logits=return_logits, record=_record)
-            loss = None if labels is None else out["loss"].reshape(())
-            lg = out["logits"]
-        logits = None if lg is None else lg.float()          # :1882 logits.float()
-        if not return_dict:
-            return ((loss,) if loss is not None else ()) + ((logits,) if logits is not None else ())
-        return self.output_class(loss=loss, logits=logits)
+        return self._forward_step(input_ids, attention_mask, labels, (pixel_values, pixel_attention_mask), self.output_class, return_dict,
+                                  return_logits, record=_record)          # :1882 logits.float()
 
 
 @dataclass
-class SequenceClassifierOutputWithPast:
+class SequenceClassifierOutputWithPast(BB.ModelOutput):
     """transformers.modeling_outputs.SequenceClassifierOutputWithPast, as the reference class returns it (modeling_idefics2.py:2216-2222)"""
     loss: Optional[torch.Tensor] = None
     logits: Optional[torch.Tensor] = None
     past_key_values: Optional[Tuple] = None
     hidden_states: Optional[Tuple] = None
     attentions: Optional[Tuple] = None
-
-    def __getitem__(self, k):
-        if isinstance(k, str):
-            return getattr(self, k)
-        return tuple(v for v in (self.loss, self.logits, self.past_key_values, self.hidden_states, self.attentions) if v is not None)[k]
 
 
 class Idefics2ForSequenceClassification(Idefics2ForConditionalGeneration):
@@ -393,24 +298,10 @@ class Idefics2ForSequenceClassification(Idefics2ForConditionalGeneration):
             raise NotImplementedError("output_attentions / output_hidden_states are not produced by the fused kernels")
         if position_ids is not None:
             raise NotImplementedError("explicit position_ids (the reference passes None: Mistral's default arange)")
-        return_dict = return_dict if return_dict is not None else self.config.use_return_dict
-        if attention_mask is None:
-            attention_mask = torch.ones_like(input_ids)
-        want_grads = self.training and labels is not None and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        if want_grads:
-            loss = self._autograd_step(lambda: self.engine.step(
-                input_ids, attention_mask, labels, pixel_values, pixel_attention_mask, grad_scale=1.0, loss_scale=1.0, compute_grads=True,
-                overwrite_grads=True, record=_record))
-            logits = self._last_logits
-        else:
-            # evaluation (Trainer.evaluate / prediction_step under no_grad): the same pooled logits and loss, no backward
-            out = self.engine.step(input_ids, attention_mask, labels, pixel_values, pixel_attention_mask, compute_grads=False,
-                                   record=_record)
-            loss = None if labels is None else out["loss"].reshape(())
-            logits = out["logits"]
-        if not return_dict:
-            return ((loss,) if loss is not None else ()) + (logits,)
-        return SequenceClassifierOutputWithPast(loss=loss, logits=logits)
+        # training and evaluation (Trainer.evaluate / prediction_step under no_grad) alike return the pooled logits: the classification
+        # leg of the engine step does not read need_logits, return_logits = True only keeps the helper from deciding
+        return self._forward_step(input_ids, attention_mask, labels, (pixel_values, pixel_attention_mask), SequenceClassifierOutputWithPast,
+                                  return_dict, True, record=_record)
 
 
 class Idefics2Engine:
@@ -424,6 +315,7 @@ class Idefics2Engine:
         self._verified = False
         self.w8 = None                       # decoder_fp8.Fp8Weights after model.set_precision("fp8")
         self.weights_unchanged = False       # set by MantisHipTrainer on the 2nd.. micro-batch of an accumulation window
+        self._prefetched = BB.PrefetchSlots()     # (pixel_values object, feats, N, I, km_all, done event) of prefetch_vision
 
     def step_from_batch(self, inputs, launch=None, **kw):
         """launch: the caller's `launch.LaunchContext`, in force for exactly this call (see engine.LlavaEngine.step_from_batch)"""
@@ -512,33 +404,20 @@ class Idefics2Engine:
             feats, N = self.vision_forward(pix, pos_ids, vit_kmask)
             done = torch.cuda.Event()
             done.record(stream)
-        slots = self.__dict__.setdefault("_prefetched", {})
-        slots[id(pv)] = (pv, feats, N, pix.shape[0], km_all, done)
-        while len(slots) > 2:                               # a prefetched batch that never arrives must not pile up
-            slots.pop(next(iter(slots)))
+        self._prefetched.put(pv, feats, N, pix.shape[0], km_all, done)
 
     # ------------------------------------------------------------------ vision tower (frozen, forward only)
     def vision_forward(self, pix, pos_ids, kmask):
         m, vc = self.m, self.cfg.vision_config
         vt = m.vt
         I = pix.shape[0]
-        P, dv = vc.patch_size, vc.hidden_size
+        P = vc.patch_size
         N = (pix.shape[2] // P) * (pix.shape[3] // P)
         patches = K.im2col(pix, P, vt["patch_kp"])
         pe = K.gemm_nt(patches, vt["patch_w_padded"](), bias=vt["patch_b"])
         x = K.add(pe, K.gather_rows(vt["pos"], pos_ids.reshape(-1)))
-        eps = vc.layer_norm_eps
-        nh = vc.num_attention_heads
-        hd = dv // nh
-        for lw in vt["layers"]:
-            y = K.layernorm_fwd(x, lw["ln1_w"], lw["ln1_b"], eps)
-            qkv = K.gemm_nt(y, lw["qkv_w"], bias=lw["qkv_b"])
-            o, _ = K.attn_fwd(qkv, I, N, nh, nh, hd, kmask, hd ** -0.5, False, want_lse=False)
-            x = K.gemm_nt(o, lw["out_w"], bias=lw["out_b"], residual=x)
-            y = K.layernorm_fwd(x, lw["ln2_w"], lw["ln2_b"], eps)
-            hmid = K.gemm_nt(y, lw["fc1_w"], bias=lw["fc1_b"], act=vc.hidden_act)
-            x = K.gemm_nt(hmid, lw["fc2_w"], bias=lw["fc2_b"], residual=x)
-        return K.layernorm_fwd(x, vt["post_ln"][0], vt["post_ln"][1], eps), N
+        x = BB.vit_encoder(K, vt["layers"], x, I, N, vc, kmask)
+        return K.layernorm_fwd(x, vt["post_ln"][0], vt["post_ln"][1], vc.layer_norm_eps), N
 
     # ------------------------------------------------------------------ connector forward (saves what its backward needs)
     def connector_forward(self, feats, I, N, km_all, record=None):
@@ -636,10 +515,10 @@ class Idefics2Engine:
              compute_grads=True, overwrite_grads=True, need_logits=False, record=None, on_bucket_ready=None, segment_ids=None):
         m, cfg, tc = self.m, self.cfg, self.cfg.text_config
         dev = m.device
-        ids_cpu = input_ids.detach().to("cpu") if input_ids.device.type != "cpu" else input_ids
+        ids_cpu = BB.to_host(input_ids)
         B, T = ids_cpu.shape
         IMG = cfg.image_token_id
-        am_cpu = attention_mask.detach().to("cpu") if attention_mask.device.type != "cpu" else attention_mask
+        am_cpu = BB.to_host(attention_mask)
         ids_d = input_ids.to(dev, non_blocking=True)
         attn_d = attention_mask.to(dev, non_blocking=True).to(torch.int64)
         seqcls = m.head_kind == "seqcls"          # classification head: `labels` are per-sample targets, not token ids
@@ -657,8 +536,8 @@ class Idefics2Engine:
         n_rows = 0
         is_img = ids_cpu == IMG
         if pixel_values is not None:
-            pre = self.__dict__.get("_prefetched", {}).pop(id(pixel_values), None)
-            if pre is not None and pre[0] is pixel_values and record is None:
+            pre = self._prefetched.take(pixel_values)
+            if pre is not None and record is None:
                 feats, N, I, km_all = pre[1], pre[2], pre[3], pre[4]        # computed ahead on another stream (prefetch_vision)
                 torch.cuda.current_stream().wait_event(pre[5])
                 for t in (feats, km_all):

@@ -18,6 +18,7 @@ Out of scope: generation / KV cache, the image processor and its tile splitting,
 (`set_precision("fp8")` refuses by name)."""
 import torch
 
+from . import backbone as BB
 from . import modeling_idefics2 as I2       # the engine's operators are I2.K: tests monkeypatch that one name
 from .configuration_idefics3 import Idefics3Config
 from .modeling_idefics2 import Idefics2CausalLMOutputWithPast, Idefics2Engine, Idefics2ForConditionalGeneration
@@ -110,7 +111,7 @@ class Idefics3Engine(Idefics2Engine):
         outside [0, vocab_size) raises IndexError, as torch's CrossEntropyLoss does."""
         if labels is None:
             return
-        lab = labels.detach().to("cpu") if labels.device.type != "cpu" else labels
+        lab = BB.to_host(labels)
         V = self.cfg.text_config.vocab_size
         valid = (am_cpu != 0) & (lab != -100)
         valid[:, 0] = False

@@ -15,6 +15,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import backbone as BB
 from . import decoder as D
 from . import decoder_fp8 as D8
 from . import hip_ops as K   # tests may monkeypatch `modeling_qwen2_vl.K` with the oracle's operators to test the host logic
@@ -24,7 +25,7 @@ from .configuration_qwen2_vl import Qwen2VLConfig
 
 
 @dataclass
-class Qwen2VLCausalLMOutputWithPast:
+class Qwen2VLCausalLMOutputWithPast(BB.ModelOutput):
     """transformers/models/qwen2_vl/modeling_qwen2_vl.py:84-93"""
     loss: Optional[torch.Tensor] = None
     logits: Optional[torch.Tensor] = None
@@ -32,12 +33,6 @@ class Qwen2VLCausalLMOutputWithPast:
     hidden_states: Optional[Tuple] = None
     attentions: Optional[Tuple] = None
     rope_deltas: Optional[torch.Tensor] = None
-
-    def __getitem__(self, k):
-        if isinstance(k, str):
-            return getattr(self, k)
-        return tuple(v for v in (self.loss, self.logits, self.past_key_values, self.hidden_states, self.attentions, self.rope_deltas)
-                     if v is not None)[k]
 
 
 def _param_specs(cfg: Qwen2VLConfig):
@@ -54,21 +49,13 @@ def _param_specs(cfg: Qwen2VLConfig):
               (p + "attn.proj.bias", (dv,)), (p + "mlp.fc1.weight", (iv, dv)), (p + "mlp.fc1.bias", (iv,)),
               (p + "mlp.fc2.weight", (dv, iv)), (p + "mlp.fc2.bias", (dv,))]
     dm = dv * mg * mg
-    d, it, V = tc.hidden_size, tc.intermediate_size, tc.vocab_size
-    H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
+    d, V = tc.hidden_size, tc.vocab_size
     s += [(v + "merger.ln_q.weight", (dv,)), (v + "merger.ln_q.bias", (dv,)), (v + "merger.mlp.0.weight", (dm, dm)),
           (v + "merger.mlp.0.bias", (dm,)), (v + "merger.mlp.2.weight", (d, dm)), (v + "merger.mlp.2.bias", (d,))]
     t = "model.language_model."
     s.append((t + "embed_tokens.weight", (V, d)))
     for i in range(tc.num_hidden_layers):
-        p = f"{t}layers.{i}."
-        # [norms | q k v weights | q k v biases | o] [gate up] [down] = reverse of backward completion (DP sub-buckets)
-        s += [(p + "input_layernorm.weight", (d,)), (p + "post_attention_layernorm.weight", (d,)),
-              (p + "self_attn.q_proj.weight", (H * hd, d)), (p + "self_attn.k_proj.weight", (Hkv * hd, d)),
-              (p + "self_attn.v_proj.weight", (Hkv * hd, d)),
-              (p + "self_attn.q_proj.bias", (H * hd,)), (p + "self_attn.k_proj.bias", (Hkv * hd,)), (p + "self_attn.v_proj.bias", (Hkv * hd,)),
-              (p + "self_attn.o_proj.weight", (d, H * hd)),
-              (p + "mlp.gate_proj.weight", (it, d)), (p + "mlp.up_proj.weight", (it, d)), (p + "mlp.down_proj.weight", (d, it))]
+        s += BB.decoder_layer_specs(f"{t}layers.{i}.", tc, qkv_bias=True)      # q k v biases between v_proj.weight and o_proj.weight
     s += [(t + "norm.weight", (d,)), ("lm_head.weight", (V, d))]
     return s
 
@@ -116,60 +103,27 @@ class Qwen2VLForConditionalGeneration(ArenaModule):
                        ln_q=(g(v + "merger.ln_q.weight"), g(v + "merger.ln_q.bias")),
                        m0_w=g(v + "merger.mlp.0.weight"), m0_b=g(v + "merger.mlp.0.bias"),
                        m2_w=g(v + "merger.mlp.2.weight"), m2_b=g(v + "merger.mlp.2.bias"))
-        d, it = tc.hidden_size, tc.intermediate_size
-        H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
         t = "model.language_model."
-        ll = []
-        for i in range(tc.num_hidden_layers):
-            p = f"{t}layers.{i}."
-            ll.append(dict(qkv=self._flat(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", (H + 2 * Hkv) * hd, d),
-                           qkv_b=self._flat(p + "self_attn.q_proj.bias", p + "self_attn.v_proj.bias", 1, (H + 2 * Hkv) * hd).view(-1),
-                           o=g(p + "self_attn.o_proj.weight"),
-                           gu=self._flat(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", 2 * it, d), down=g(p + "mlp.down_proj.weight"),
-                           ln1=g(p + "input_layernorm.weight"), ln2=g(p + "post_attention_layernorm.weight")))
+        ll = [BB.decoder_layer_views(f"{t}layers.{i}.", tc, g, self._flat, qkv_bias=True) for i in range(tc.num_hidden_layers)]
         self.lm = dict(embed=g(t + "embed_tokens.weight"), layers=ll, norm=g(t + "norm.weight"), head=g("lm_head.weight"))
 
     def _build_grad_views(self):
         tc = self.config.text_config
         gv = self._grad_views.get
-        d, it = tc.hidden_size, tc.intermediate_size
-        H, Hkv, hd = tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim
         t = "model.language_model."
         self.grads = dict(head=gv("lm_head.weight"), norm=gv(t + "norm.weight"), embed=gv(t + "embed_tokens.weight"))
-        self.grads_layers = []
-        for i in range(tc.num_hidden_layers):
-            p = f"{t}layers.{i}."
-            qb = self._gflat(p + "self_attn.q_proj.bias", p + "self_attn.v_proj.bias", 1, (H + 2 * Hkv) * hd)
-            self.grads_layers.append(dict(
-                qkv=self._gflat(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", (H + 2 * Hkv) * hd, d),
-                qkv_b=None if qb is None else qb.view(-1), o=gv(p + "self_attn.o_proj.weight"),
-                gu=self._gflat(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", 2 * it, d), down=gv(p + "mlp.down_proj.weight"),
-                ln1=gv(p + "input_layernorm.weight"), ln2=gv(p + "post_attention_layernorm.weight")))
+        self.grads_layers = [BB.decoder_layer_views(f"{t}layers.{i}.", tc, gv, self._gflat, qkv_bias=True)
+                             for i in range(tc.num_hidden_layers)]
 
-    @torch.no_grad()
-    def reset_parameters(self, seed=0):
-        """normal(0, initializer_range), norm weights 1, biases 0 (HF PreTrainedModel._init_weights)."""
-        std = self.config.text_config.get("initializer_range", 0.02)
-        self._param_version += 1
-        gen = torch.Generator(device=self.device).manual_seed(seed)
-        for name, p in self.named_parameters():
-            if p.dim() == 1:
-                p.fill_(1.0 if (("norm" in name or "ln_q" in name) and name.endswith("weight")) else 0.0)
-            else:
-                flat = p.view(-1)
-                step = 1 << 26
-                for a in range(0, flat.numel(), step):
-                    b = min(flat.numel(), a + step)
-                    flat[a:b] = torch.randn(b - a, generator=gen, device=self.device, dtype=torch.float32).mul_(std)
+    def _init_value(self, name, p):
+        """HF PreTrainedModel._init_weights; the merger's `ln_q` is a LayerNorm too"""
+        return 1.0 if name.endswith("ln_q.weight") else super()._init_value(name, p)
 
     def get_input_embeddings(self):
         return self.model.language_model.embed_tokens
 
     def get_output_embeddings(self):
         return self.lm_head
-
-    def tie_weights(self, *a, **k):
-        return None
 
     def load_reference_state_dict(self, sd, strict=True):
         return self.copy_state_dict(sd, rename=_rename_hf4, ignorable=lambda k: k.endswith("inv_freq"), strict=strict)
@@ -179,13 +133,9 @@ class Qwen2VLForConditionalGeneration(ArenaModule):
         'attn'), then 'front' = token embedding."""
         self._ensure_grad_arena()
         span = self._bucket_span
-        out = {"head": span(lambda n: n.startswith("model.language_model.norm") or n.startswith("lm_head"))}
-        for i in range(self.config.text_config.num_hidden_layers):
-            p = f"model.language_model.layers.{i}."
-            out[("layer", i, "down")] = span(lambda n: n == p + "mlp.down_proj.weight")
-            out[("layer", i, "gu")] = span(lambda n: n in (p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"))
-            out[("layer", i, "attn")] = span(lambda n: n.startswith(p) and ".mlp." not in n)
-        out["front"] = span(lambda n: n.startswith("model.language_model.embed_tokens"))
+        out = {"head": span(lambda n: n.startswith("model.language_model.norm") or n.startswith("lm_head")),
+               **BB.decoder_buckets(span, "model.language_model.layers.", self.config.text_config.num_hidden_layers),
+               "front": span(lambda n: n.startswith("model.language_model.embed_tokens"))}
         return {k: v for k, v in out.items() if v is not None}
 
     # ------------------------------------------------------------------ forward (HF Qwen2VLForConditionalGeneration.forward :1245-1338)
@@ -201,27 +151,8 @@ class Qwen2VLForConditionalGeneration(ArenaModule):
             raise NotImplementedError("output_attentions / output_hidden_states are not produced by the fused kernels")
         if position_ids is not None:
             raise NotImplementedError("explicit position_ids (the reference passes None: the 3-D rope index is derived from the batch)")
-        return_dict = return_dict if return_dict is not None else self.config.use_return_dict
-        if attention_mask is None:
-            attention_mask = torch.ones_like(input_ids)
-        want_grads = self.training and labels is not None and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        if return_logits is None:
-            return_logits = not want_grads        # training: the [B,L,V] logits are never materialised unless asked for
-        if want_grads:
-            # stock `loss.backward()` callers: the fused forward+backward runs now, .backward() publishes the gradients (arena.FusedStep)
-            loss = self._autograd_step(lambda: self.engine.step(
-                input_ids, attention_mask, labels, pixel_values, image_grid_thw, grad_scale=1.0, loss_scale=1.0, compute_grads=True,
-                overwrite_grads=True, need_logits=return_logits, record=_record))
-            lg = self._last_logits
-        else:
-            out = self.engine.step(input_ids, attention_mask, labels, pixel_values, image_grid_thw, compute_grads=False,
-                                   need_logits=return_logits, record=_record)
-            loss = None if labels is None else out["loss"].reshape(())
-            lg = out["logits"]
-        logits = None if lg is None else lg.float()
-        if not return_dict:
-            return ((loss,) if loss is not None else ()) + ((logits,) if logits is not None else ())
-        return Qwen2VLCausalLMOutputWithPast(loss=loss, logits=logits)
+        return self._forward_step(input_ids, attention_mask, labels, (pixel_values, image_grid_thw), Qwen2VLCausalLMOutputWithPast,
+                                  return_dict, return_logits, record=_record)
 
 
 # ---------------------------------------------------------------------- host-side integer bookkeeping (tiny, data dependent)
@@ -300,7 +231,7 @@ class Qwen2VLEngine:
         # since the last one), so the fp8 weight copies are reused; any other caller gets a fresh quantisation every step
         self.weights_unchanged = False
         self._side = None                    # side stream of prefetch_vision
-        self._prefetched = {}                # id(pixel_values object) -> (pixel_values object, image rows, done event)
+        self._prefetched = BB.PrefetchSlots()     # (pixel_values object, image rows, done event) of prefetch_vision
 
     # ------------------------------------------------------------------ software pipelining of the frozen tower
     def prefetch_vision(self, inputs, after_event=None, stream=None, launch=None):
@@ -324,9 +255,7 @@ class Qwen2VLEngine:
             img = self.vision_forward(pix, grids)
             done = torch.cuda.Event()
             done.record(stream)
-        self._prefetched[id(pv)] = (pv, img, done)
-        while len(self._prefetched) > 2:                   # a prefetched batch that never arrives must not pile up
-            self._prefetched.pop(next(iter(self._prefetched)))
+        self._prefetched.put(pv, img, done)
 
     def step_from_batch(self, inputs, launch=None, **kw):
         """launch: the caller's `launch.LaunchContext`, in force for exactly this call (see engine.LlavaEngine.step_from_batch)"""
@@ -391,12 +320,12 @@ class Qwen2VLEngine:
              compute_grads=True, overwrite_grads=True, need_logits=False, record=None, on_bucket_ready=None, segment_ids=None):
         m, cfg, tc = self.m, self.cfg, self.cfg.text_config
         dev = m.device
-        ids_cpu = input_ids.detach().to("cpu") if input_ids.device.type != "cpu" else input_ids
+        ids_cpu = BB.to_host(input_ids)
         B, T = ids_cpu.shape
         IMG = cfg.image_token_id
-        am_cpu = attention_mask.detach().to("cpu") if attention_mask.device.type != "cpu" else attention_mask
+        am_cpu = BB.to_host(attention_mask)
         if labels is not None:                  # host-only check, every step
-            lab_cpu = labels.detach().to("cpu") if labels.device.type != "cpu" else labels
+            lab_cpu = BB.to_host(labels)
             if bool((lab_cpu[am_cpu == 0] != -100).any()):
                 raise NotImplementedError("labels != -100 where attention_mask == 0 (HF's loss would count them; the reference's collator "
                                           "never produces them)")
@@ -410,8 +339,8 @@ class Qwen2VLEngine:
             if image_grid_thw is None:
                 raise ValueError("pixel_values without image_grid_thw")
             grids = [tuple(int(v) for v in g) for g in torch.as_tensor(image_grid_thw).tolist()]
-            pre = self._prefetched.pop(id(pixel_values), None)
-            if pre is not None and pre[0] is pixel_values and record is None:
+            pre = self._prefetched.take(pixel_values)
+            if pre is not None and record is None:
                 img = pre[1]                                   # computed ahead on the side stream (prefetch_vision)
                 torch.cuda.current_stream().wait_event(pre[2])
                 img.record_stream(torch.cuda.current_stream())
@@ -426,12 +355,12 @@ class Qwen2VLEngine:
                 raise ValueError(f"Image features and image tokens do not match, tokens: {n_tok}, features: {n_rows}")
             if bool((am_cpu[ids_cpu == IMG] == 0).any()):
                 raise NotImplementedError("attention_mask == 0 on an <|image_pad|> token")
-            seg_cpu = None if segment_ids is None else (segment_ids.detach().to("cpu") if segment_ids.device.type != "cpu" else segment_ids)
+            seg_cpu = None if segment_ids is None else BB.to_host(segment_ids)
             pos3 = mrope_position_ids(ids_cpu, am_cpu, grids, IMG, mg, seg_cpu)
         elif segment_ids is None:
             pos3 = torch.arange(T, dtype=torch.int64)[None, None].expand(3, B, T).contiguous()   # text only: HF counts 0..T-1 itself
         else:
-            seg_cpu = segment_ids.detach().to("cpu") if segment_ids.device.type != "cpu" else segment_ids
+            seg_cpu = BB.to_host(segment_ids)
             pos3 = mrope_position_ids(ids_cpu, torch.ones_like(ids_cpu), [], IMG, mg, seg_cpu)   # arange restarting at every sample
         # masked_scatter (:1160-1166) = the packing plan with ONE slot per <|image_pad|> token, rows taken in order
         plan = K.pack_plan(ids_d, attn_d, lab_d, 1, n_rows, IMG if img is not None else -(2 ** 62), -1, -100, T)

@@ -144,3 +144,28 @@ def test_optimizer_state_records_the_alignment_it_was_laid_out_with(monkeypatch)
     o.load_state_dict(sd)                                       # round trip
     with pytest.raises(ValueError, match="aligned to 8 elements"):
         o.load_state_dict(dict(sd, arena_align=8))
+
+
+@pytest.fixture(scope="module")
+def layout_fixture():
+    import json
+    import os
+    with open(os.path.join(Hh.G, "arena_layout.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("name", ["llava_siglip", "llava_clip", "idefics2", "idefics2_seqcls", "qwen2vl", "idefics3"])
+def test_layout_buckets_and_init_match_the_recorded_fixture(layout_fixture, name):
+    """Every parameter's (name, shape, offset), every gradient bucket's (key, offset, numel) and the arena bytes after
+    `reset_parameters(0)` equal what tests/golden/make_arena_layout.py recorded: the shared plumbing (mantis_amd/backbone.py, arena.py) must
+    not move a tensor, a bucket or a drawn value.  Lists are compared, not digests, so a mismatch names the tensor."""
+    from tests.golden import make_arena_layout as mk
+    assert torch.__version__ == layout_fixture["torch_version"], (
+        f"tests/golden/arena_layout.json was recorded with torch {layout_fixture['torch_version']}, this is {torch.__version__}: the seed-0 "
+        "digests depend on torch's CPU generator -- run tests/golden/make_arena_layout.py again (on a commit whose layout is known good)")
+    want = layout_fixture["models"][name]
+    got = mk.record(mk.builders()[name]())
+    assert got["layout"] == want["layout"]
+    assert got["buckets"] == want["buckets"]
+    assert (got["arena_numel"], got["grad_arena_numel"]) == (want["arena_numel"], want["grad_arena_numel"])
+    assert got["init_sha256"] == want["init_sha256"]
