@@ -88,10 +88,14 @@ __device__ __forceinline__ float act_grad(float x, int kind) {
             const float k = 0.7978845608028654f;
             const float inner = k * (x + 0.044715f * x * x * x);
             const float t = tanhf(inner);
-            return 0.5f * (1.f + t) + 0.5f * x * (1.f - t * t) * k * (1.f + 3.f * 0.044715f * x * x);
+            // saturated tanh (|x| > ~5.5): the second term is 0; evaluated as written it is 0 * inf = NaN once x * x overflows (|x| > 1.8e19)
+            const float sech2 = 1.f - t * t;
+            if (sech2 == 0.f) return 0.5f * (1.f + t);
+            return 0.5f * (1.f + t) + 0.5f * x * sech2 * k * (1.f + 3.f * 0.044715f * x * x);
         }
         case 2: {
             const float s = sigmoidf_(1.702f * x);
+            if (s == 0.f || s == 1.f) return s;            // saturated: 1.702 x overflows for |x| > 2e38 and inf * 0 = NaN
             return s + 1.702f * x * s * (1.f - s);
         }
         default: {

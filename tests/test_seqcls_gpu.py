@@ -48,6 +48,47 @@ def make_labels(problem, B, C, g):
     return torch.rand(B, C, generator=g) * 4 + 1
 
 
+ROW_BAR = 2 * 2.0 ** -8
+
+
+def rows_close(got, want, what):
+    """rel-L2 of every ROW of a bf16 gradient against the fp32 restatement: a wrong pooled row of dx or class row of dW must not hide in
+    the whole-tensor norm.  The kernels (csrc/seqcls.hip) keep everything in fp32 and round each output element to bf16 once, at most
+    2^-8 of the element and so of the row; a second 2^-8 covers the fp32 arithmetic (the cancelling g - xhat . mean(g . xhat) of dx, sums
+    over B and C in another order) and the last-place differences of the logits upstream.  A zero row of the restatement must be zero."""
+    got, want = got.double().cpu().reshape(want.shape[0], -1), want.double().cpu().reshape(want.shape[0], -1)
+    num, den = (got - want).norm(dim=1), want.norm(dim=1)
+    zero = den < 1e-12
+    assert not bool((zero & (got.norm(dim=1) >= 1e-6)).any()), what
+    err = torch.where(zero, torch.zeros_like(num), num / den.clamp_min(1e-300))
+    assert float(err.max()) <= ROW_BAR, f"{what}: worst row rel-L2 {float(err.max()):.3e} > {ROW_BAR:.3e} at row {int(err.argmax())}"
+    return float(err.max())
+
+
+def logits_close(logits, nf, W, bias, what):
+    """every logit (fp32) of every sample against the fp64 product of the kernel's OWN normalised row: d fp32 additions in any order cost
+    at most d . 2^-24 . (sum |nf| |W| + |b|), doubled for the second-order terms (tests/local_error.py gemm_bound's `acc`)"""
+    nf64, W64, b64 = nf.double().cpu(), W.double().cpu(), bias.double().cpu()
+    ref = nf64 @ W64.t() + b64
+    bound = 2.0 * nf.shape[1] * 2.0 ** -24 * (nf64.abs() @ W64.abs().t() + b64.abs())
+    ratio = (logits.double().cpu() - ref).abs() / bound.clamp_min(1e-300)
+    assert float(ratio.max()) <= 1.0, f"{what}: logit {divmod(int(ratio.argmax()), ratio.shape[1])} (sample, class) is {float(ratio.max()):.3g} x its bound"
+    return float(ratio.max())
+
+
+def nf_close(nf, x_rows, nw, eps, what):
+    """the normalised row bf16(bf16(x . rstd) . w) per element against the same chain from an fp64 rstd: the kernel's fp32 rstd may turn a
+    tie of the first rounding (1 ulp, up to 2^-7 of the value), which the second rounding can carry to 3 ulps of a result in a finer
+    binade; nothing else differs"""
+    from tests import local_error as LE
+    x64 = x_rows.double().cpu()
+    rstd = torch.rsqrt(x64.pow(2).mean(-1, keepdim=True) + eps)
+    y = (x64 * rstd).float().to(BF).double() * nw.double().cpu()
+    ulp = LE.ulp_distance_bf16(nf.cpu(), y)
+    assert int(ulp.max()) <= 3, f"{what}: nf element {divmod(int(ulp.argmax()), ulp.shape[1])} (sample, column) is {int(ulp.max())} ulps off"
+    return int(ulp.max())
+
+
 def close(got, want, what):
     got, want = got.float().cpu().numpy(), want.float().cpu().numpy()
     if np.linalg.norm(want) < 1e-12:
@@ -93,6 +134,12 @@ def test_head_kernels_match_restatement(d, C, B):
         close(gb, ref["db"], what + " db")
         close(gn, ref["dnorm"], what + " dnorm")
         close(dx, ref["dx"], what + " dx")
+        # localised: the normalised row per element, every logit per sample, dW per class row, dx per pooled row
+        rows = r["rows"].long()
+        nf_close(r["nf"], x[rows], nw, eps, what + " nf")
+        logits_close(logits, r["nf"], W, bias, what + " logits")
+        rows_close(gW, ref["dW"], what + " dW row")
+        rows_close(dx[rows], ref["dx"][rows], what + " dx row")
         off = torch.ones(B * T, dtype=torch.bool, device=DEV)
         off[r["rows"].long()] = False
         assert not dx[off].any(), what + ": dx must be exactly zero off the pooled rows"
@@ -103,6 +150,8 @@ def test_head_kernels_match_restatement(d, C, B):
         torch.cuda.synchronize()
         assert abs(float(r2["loss"]) - 0.5 * float(ref["loss"])) <= 5e-3 * abs(0.5 * float(ref["loss"])) + 1e-12
         close(aW, 1.5 * ref["dW"], what + " dW accumulate")
+        # accumulate reads the bf16 gW (2^-8 of dW), adds the halved run in fp32 and rounds (2^-8 of 1.5 dW): 2.5 / 1.5 . 2^-8 of the sum
+        rows_close(aW, 1.5 * ref["dW"], what + " dW row accumulate")
         close(ab, 1.5 * ref["db"], what + " db accumulate")
         close(an, 1.5 * ref["dnorm"], what + " dnorm accumulate")
 
