@@ -102,7 +102,8 @@ int mantis_rope_apply(void* x, const void* cos_tab, const void* sin_tab, int64_t
 int mantis_transpose(const void* in, void* out, int R, int C, int Rpad, int64_t ld_in, int64_t ld_out, int nb, int nh,
                      int64_t in_stride_b, int64_t in_stride_h, int64_t out_stride_b, int64_t out_stride_h, void* stream);
 
-/* ---- GEMM: every nn.Linear of the path (see csrc/gemm.hip).  C = epi(A[M,K] . B[N,K]^T).
+/* ---- GEMM: every nn.Linear of the path (see csrc/gemm.hip; every launch decision below -- variant, K split, CU budget, operand
+ * checks -- is host arithmetic in csrc/gemm_plan.h).  C = epi(A[M,K] . B[N,K]^T).
  * flags: 1 bias | act<<1 (1 gelu-erf, 2 gelu-tanh, 3 quick-gelu) | 16 residual add | 32 accumulate into C
  *        | 64 SwiGLU backward fused behind dact = A.B^T: residual = [gate | up][M, 2N], C = [dgate | dup][M, 2N]
  *        | bits 8-11 tile variant (0 = auto) | 4096 A is K-major ([K,M], row stride lda) | 8192 B is K-major ([K,N]):

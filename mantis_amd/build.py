@@ -16,7 +16,7 @@ SOURCES = ["pack", "norm", "act", "rope", "ce", "seqcls", "vit","gemm", "gemm176
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast"]
 # attn_fwd64: the hand-placed instruction stream wants one VALU instruction per source operation (no v_pk_* packing of f32 pairs)
 EXTRA_FLAGS = {"attn_fwd64": ["-fno-slp-vectorize"]}
-HEADERS = ["common.h", "attn_common.h", "gemm_ring.h", "attn_fwd_body.inc", "attn_bwd_dq_body.inc", "attn_bwd_dkv_body.inc",
+HEADERS = ["common.h", "attn_common.h", "gemm_ring.h", "gemm_plan.h", "gemm_flags.h", "attn_fwd_body.inc", "attn_bwd_dq_body.inc", "attn_bwd_dkv_body.inc",
            "attn_bwd_dkv_g4_body.inc", "attn_fwd64_body.inc"]
 
 

@@ -332,8 +332,6 @@ __device__ __forceinline__ void read_frags_km(bf16x8 (&dst)[N_], unsigned slab, 
 // write fp32 partials to slabs, publish (agent-scope release) and take a ticket; the last arriver acquires and sums the slabs in
 // part order -- the result does not depend on who is last (bitwise reproducible), nobody waits (no co-residency assumption),
 // and the counter is left at zero for the next launch.
-#define SK_SLAB_FLOATS (256 * 256)
-#define SK_MAX_ROUNDS 1                      // sub-rounds the remainder tiles' K parts may run as (workspace = SK_MAX_ROUNDS * #CU slabs)
 
 template <int TM, int TN>
 __device__ __forceinline__ void sk_store(const f32x16 (&acc)[TN][TM], float* __restrict__ slab, int tid) {
@@ -716,24 +714,6 @@ __device__ unsigned long long g_ring16_stamps[8192 * 8];
 // slab c; the segment that BEGINS tile t (t >= 1) from a range started in tile t - 1 -> slab units + t - 1 (at most one per tile boundary).
 // The finishing kernel adds a tile's parts in K order.  Boundaries closer than SK_MINSEG steps to a tile boundary snap onto it (no 1-step
 // segments).
-#define SK_MINSEG 4
-#define SK_BALANCED_MIN_STEPS 16            // ranges shorter than this: the equal split (its parts are >= 8 steps)
-#define SK_BALANCED_MIN_GAIN 24             // K-steps per CU the balanced round must save over the equal split to be chosen
-#define SK_EMPTY 0xFFFFu
-struct SkPlan {
-    int units;                              // 0: equal split (S parts per tile, slab rt * S + part)
-    int nspan;                              // slots of the tail region (a multiple of 8)
-    unsigned short span[256];               // slot i (XCD i % 8): the range whose second segment runs there, or SK_EMPTY
-};
-// first step of range c (0 .. units) in the remainder's step sequence; T = rem * nk
-// (32-bit on purpose: c <= 256 and T < 2^23, see sk_make_plan -- a 64-bit division is ~300 scalar instructions in a workgroup's prologue)
-__host__ __device__ __forceinline__ int sk_bound(int c, int units, int T, int nk) {
-    unsigned a = (unsigned)c * (unsigned)T / (unsigned)units;
-    const unsigned r = a % (unsigned)nk;
-    if (r < SK_MINSEG) a -= r;
-    else if ((unsigned)nk - r < SK_MINSEG) a += (unsigned)nk - r;
-    return (int)a;
-}
 
 // Two problems in ONE grid (round 6b): two weight-gradient GEMMs of a decoder layer that share K (the token count) and are independent of each
 // other -- dW(down_proj) 4096 x 14336 = 896 tiles (3.5 rounds on 256 CUs) and dW(q|k|v) 6144 x 4096 = 384 tiles (1.5 rounds), each with a K-split
@@ -1201,14 +1181,8 @@ __global__ __launch_bounds__(WPB * 64) void gemm_ring16_finish_kernel(
                                                    m0 + wm * 128 + pm * 64, n0, tile_id, aux0, aux1, aux_ld, aux_n);
 }
 
-// split-K workspace (caller-owned, see mantis_gemm_workspace_bytes): [ticket counters: (#CU + 1) u32, padded to 256 B][#CU fp32
-// slabs of 256 x 256].  Zero-initialised by the caller ONCE; every launch leaves the counters at zero (the last arriver of a
-// tile resets its ticket), so one workspace serves any number of stream-ordered launches.  No allocation, no global state here.
+// ---- host side: every decision of a launch is taken in gemm_plan.h (host-only); here the one runtime query it needs, and the launches
 static int g_num_cu[64];
-static inline size_t sk_cnt_bytes(int cus) { return (((size_t)(cus + 1) * sizeof(unsigned int)) + 255) / 256 * 256; }
-// slabs: #CU for the equal split; the balanced remainder round (SkPlan) needs one per range (<= #CU) + one per crossed tile boundary (< #CU)
-static inline size_t sk_ws_bytes(int cus) { return sk_cnt_bytes(cus) + (size_t)(SK_MAX_ROUNDS > 2 ? SK_MAX_ROUNDS : 2) * cus * SK_SLAB_FLOATS * sizeof(float); }
-
 static int num_cus() {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
@@ -1219,228 +1193,59 @@ static int num_cus() {
     }
     return g_num_cu[dev];
 }
+static inline int budget(int req) { return plan_cus(req > 0 ? req : 0, num_cus()); }
 
-// CU budget of the tile scheduler.  Rounds, the K split of an incomplete last round and the kernel choice are planned for plan_cus(req)
-// compute units: all of the device by default; fewer when something else holds CUs for the length of a GEMM -- every RCCL channel is a
-// workgroup that cannot share a CU with a ring workgroup (160 KiB of LDS each), so with C channels busy a launch planned for 256 CUs
-// runs its "one round" as two.  The budget is a PER-CALL argument (bits 16-27 of `flags`; round 5 -- until round 4 a process-wide
-// variable, which let two models / reducers of one process interfere); 0 = the default, MANTIS_GEMM_CUS (an environment constant,
-// read once) or the whole device.  The split-K workspace is always sized for the whole device, so any budget fits it.  Results are
-// deterministic for a given budget; across budgets the K-split of the remainder tiles differs, i.e. the fp32 summation order of those
-// tiles (bf16 results agree to rounding, not bit for bit).
-static int plan_cus(int req) {
-    const int dev = num_cus();
-    if (req <= 0) {
-        static int env = -1;              // the process' configuration constant, never written after the first read
-        if (env < 0) {
-            const char* e = getenv("MANTIS_GEMM_CUS");
-            const int v = e ? atoi(e) : 0;
-            env = v > 0 ? v : 0;
-        }
-        req = env;
-    }
-    if (req == 0) return dev;
-    return req < 8 ? 8 : (req > dev ? dev : req);
-}
-static inline int flags_cus(int flags) { return (flags & EPI_CUS_MASK) >> EPI_CUS_SHIFT; }
-
-// K parts for the tiles of the ring kernel's incomplete last round: minimise K-steps per part + the measured reduction cost
-// (slab write, publish, S slab reads by the last arriver ~ 8 + 1.7 S K-step equivalents; sc1 write-through slabs instead of the
-// release/acquire pair were measured equal at S = 2 and 12 % slower at S = 8).  S * rem <= #CU: ONE sub-round of split units.  Round 3
-// tried letting S * rem exceed the CU count (SK_MAX_ROUNDS = 3: for dX of gate|up, 96 remainder tiles x 448 K-steps, S = 8 fills all 256
-// CUs for three short sub-rounds instead of 192 CUs for one long one; the model predicted -15 % on the remainder): measured SLOWER,
-// 984 -> 1216 us on the 8-wave kernel, 1027 -> 1481 us on the 4-wave one -- 768 slabs of 256 KiB written and read back cost far more
-// than the 8 + 1.7 S model extrapolates.  The code path stays (SK_MAX_ROUNDS), the limit is 1.
-static int ring_split(long ntiles, int nk, int cus) {
-    const int rem = (int)(ntiles % cus);
-    if (!rem) return 1;
-    int best = 1;
-    double cost = nk + 5.0, cost1 = -1.0;    // cost1: best single-sub-round split
-    int best1 = 1;
-    static int s_max = -1;                   // MANTIS_GEMM_SPLIT_MAX: cap on S (measurements)
-    if (s_max < 0) { const char* e = getenv("MANTIS_GEMM_SPLIT_MAX"); s_max = e && atoi(e) > 0 ? atoi(e) : 8; }
-    for (int S = 2; S <= s_max; ++S) {
-        if (nk / S < 8) break;
-        const int rounds = (S * rem + cus - 1) / cus;
-        if (rounds > SK_MAX_ROUNDS) break;
-        const double c = rounds * ((double)nk / S + 5.0) + 8.0 + 1.7 * S;
-        if (rounds == 1 && (cost1 < 0 || c < cost1)) { cost1 = c; best1 = S; }
-        if (c < cost) { cost = c; best = S; }
-    }
-    if (best > 1 && (best * rem + cus - 1) / cus > 1) {          // a multi-sub-round split must beat the alternatives clearly
-        const double alt = cost1 > 0 && cost1 < nk + 5.0 ? cost1 : nk + 5.0;
-        if (cost > 0.9 * alt) return cost1 > 0 && cost1 < nk + 5.0 ? best1 : 1;
-    }
-    return best;
-}
-// tile variant by a cost model fitted to measurements (profiles/r01_gemm_experiments.md), in microseconds:
-//   ring 256x256, 1 workgroup/CU: 1.45 per K-step + 5 K-step equivalents per round (prologue, epilogue, launch)
-//   generic 128x128, 2 workgroups/CU: 1.05 per K-step per round of 2 x #CU tiles + 5.2 equivalents
-static int gemm_pick_variant(int M, int N, int K, int cus_req = 0) {
-    // below two tile rows / columns the cost model decides too (M = 504 label rows of the lm_head used to fall to the 128x128 kernel
-    // -- and, on the dX side, to a transposed weight copy: 2.3 ms instead of 0.58 ms); only genuinely small operands skip it
-    if (M < 384 || N < 384) return 1;
-    const int cus = plan_cus(cus_req), nk = cdiv(K, BK);
-    const long t256 = (long)cdiv(M, 256) * cdiv(N, 256), t128 = (long)cdiv(M, 128) * cdiv(N, 128);
-    const int S = ring_split(t256, nk, cus);
-    const long rem = t256 % cus;
-    const int sub = rem ? (int)((S * rem + cus - 1) / cus) : 0;
-    const double ring = 1.45 * ((double)(t256 / cus) * (nk + 5.0) + (rem ? sub * ((double)nk / S + 5.0) + (S > 1 ? 8.0 + 1.7 * S : 0.0) : 0.0));
-    const double gen = 1.05 * (double)((t128 + 2 * cus - 1) / (2 * cus)) * (nk + 5.2);
-    return ring <= gen ? 12 : 1;
-}
-
-// ring kernel per shape (measured, profiles/r03_gemm_ring_variants.md)
-// (1x MI355X, the fifteen GEMMs of a Mantis-8B decoder layer + head, every layout): the 8-wave 16x16x32 kernel (14) is 2-7 % faster than
-// the 32x32x16 one (12) on twelve of them and within 3 % on the rest; the 4-wave kernel (13) is faster still -- 4-5 % over 14 -- where the
-// main loop is all there is: row-major operands (NT) and a long per-CU K walk (rounds x K-steps), and slower everywhere else (its
-// prologue, epilogue and K-split reduction run on half the waves)
-static int ring_variant_for(int M, int N, int K, bool akm, bool bkm, int cus_req = 0) {
-    if (akm || bkm) return 14;
-    const long tiles = (long)cdiv(M, 256) * cdiv(N, 256);
-    const long rounds = (tiles + plan_cus(cus_req) - 1) / plan_cus(cus_req);
-    return rounds * cdiv(K, BK) >= 400 ? 13 : 14;
-}
-
-static bool sk_balanced_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MANTIS_GEMM_SK_BALANCED"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v != 0;
-}
-// the balanced remainder plan of a launch (SkPlan), or units = 0 when the equal split already fills the planned CUs / the ranges would be short
-static void sk_make_plan(SkPlan& plan, int rem, int S, int nk, int cus) {
-    plan.units = 0;
-    plan.nspan = 0;
-    const long T = (long)rem * nk;
-    if (!sk_balanced_enabled() || S * rem == cus || rem >= cus || cus > 256 || T / cus < SK_BALANCED_MIN_STEPS || T >= (1L << 23)) return;
-    // what it buys: nk / S - T / units K-steps per CU; what it costs: a second prologue + slab store on the CUs that take a tail, more
-    // slabs for the finishing pass -- measured ~25 - 30 us, i.e. ~20 K-steps (profiles/r05_experiments.md: dX(gate|up), 448 K-steps, -43 us;
-    // down_proj forward, 224, -8 us; the 64- and 96-step shapes +8 ... +16 us): only where the saving is clearly larger
-    if (nk / S - (int)(T / cus) < SK_BALANCED_MIN_GAIN) return;
-    const int U = cus;
-    if (U % 8) return;                                          // the tail placement assumes workgroup j of the remainder section runs on XCD j % 8
-    int f[8][32], idx[8][32], n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int c = 0; c < U; ++c) {
-        const int a0 = sk_bound(c, U, (int)T, nk), a1 = sk_bound(c + 1, U, (int)T, nk);
-        const int e = (a0 / nk + 1) * nk;
-        if (a1 <= a0) return;                                   // a degenerate range: keep the equal split
-        if (a1 > e) {
-            if (a1 - e > nk) return;                            // a range spanning three tiles cannot happen for rem < units; be safe
-            const int x = c & 7;
-            int j = n[x]++;                                     // insertion by first-segment length (then range index): <= 32 per XCD
-            while (j > 0 && f[x][j - 1] > e - a0) { f[x][j] = f[x][j - 1]; idx[x][j] = idx[x][j - 1]; --j; }
-            f[x][j] = e - a0;
-            idx[x][j] = c;
-        }
-    }
-    int R = 0;
-    for (int x = 0; x < 8; ++x) R = n[x] > R ? n[x] : R;
-    plan.units = U;
-    plan.nspan = 8 * R;
-    for (int r = 0; r < R; ++r)
-        for (int x = 0; x < 8; ++x) plan.span[8 * r + x] = r < n[x] ? (unsigned short)idx[x][r] : (unsigned short)SK_EMPTY;
-}
-static bool sk_finish_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MANTIS_GEMM_SK_FINISH"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v != 0;
-}
 template <bool AKM, bool BKM, bool SWIGLU = false, int R16 = 0, int PAIR = PAIR_NONE>       // R16: 0 = the 32x32x16 kernel, 4 / 8 = ring16 waves
 static int launch_gemm_ring(hipStream_t s, const bf16_t* A, const bf16_t* B, bf16_t* C, int M, int N, int K, long lda, long ldb,
                             long ldc, const bf16_t* bias, const bf16_t* res, long ldr, int flags, void* ws, long ws_bytes,
                             bf16_t* aux0 = nullptr, const bf16_t* aux1 = nullptr, long aux_ld = 0, int aux_n = 0) {
-    const int tiles_m = cdiv(M, 256), tiles_n = cdiv(N, 256), nk = cdiv(K, BK);
-    const long ntiles = (long)tiles_m * tiles_n;
-    const int cus = plan_cus(flags_cus(flags));
-    const int rem = (int)(ntiles % cus);
-    const int S = ring_split(ntiles, nk, cus);
-    const int full = S > 1 ? (int)(ntiles - rem) : (int)ntiles;
-    const int grid = S > 1 ? full + S * rem : (int)ntiles;
+    const int dev_cus = num_cus();
+    const RingPlan p = ring_make_plan(M, N, K, plan_cus(flags_cus(flags), dev_cus), R16 != 0, flags & EPI_SK_INKERNEL);
     float* slabs = nullptr;
-    unsigned int* cnt = nullptr;
-    if (S > 1) {
-        const int dev_cus = num_cus();            // the workspace layout is that of the whole device, whatever the planning budget
+    unsigned int* cnt = nullptr;           // the caller's workspace: [ticket counters][slabs], see sk_ws_bytes
+    if (p.needs_ws) {
         if (!ws || ((uintptr_t)ws & 255) || ws_bytes < (long)sk_ws_bytes(dev_cus)) return MANTIS_EINVAL;   // see mantis_gemm_workspace_bytes
         cnt = (unsigned int*)ws;
         slabs = (float*)((char*)ws + sk_cnt_bytes(dev_cus));
     }
     if constexpr (R16 != 0) {
-        // remainder tiles: the split units leave their slabs and gemm_ring16_finish_kernel reduces them on all CUs (cnt = nullptr tells the GEMM
-        // kernel); MANTIS_GEMM_SK_FINISH=0 keeps the round-4 in-kernel reduction by the last arriver (A/B measurements)
-        const bool finish = S > 1 && !(flags & EPI_SK_INKERNEL) && sk_finish_enabled();
-        SkPlan plan;
-        plan.units = 0;
-        plan.nspan = 0;
-        if (finish) sk_make_plan(plan, rem, S, nk, cus);
-        const int grid16 = plan.units ? full + plan.units + plan.nspan : grid;
-        const int S16 = plan.units ? rem : S;                  // balanced plan: the kernels take the number of remainder tiles here
-        MANTIS_LAUNCH((gemm_nt_ring16_kernel<R16, AKM, BKM, SWIGLU, PAIR>), dim3(grid16), dim3(R16 * 64), 0, s, A, B, C, M, N, K, lda, ldb, ldc,
-                           bias, res, ldr, flags, tiles_m, tiles_n, full, S16, slabs, finish ? nullptr : cnt, aux0, aux1, aux_ld, aux_n, plan, NoGroup{});
-        if (finish) {
+        // finish: the split units leave their slabs and gemm_ring16_finish_kernel reduces them on all CUs (cnt = nullptr tells the GEMM kernel)
+        MANTIS_LAUNCH((gemm_nt_ring16_kernel<R16, AKM, BKM, SWIGLU, PAIR>), dim3(p.grid16), dim3(R16 * 64), 0, s, A, B, C, M, N, K, lda, ldb, ldc,
+                           bias, res, ldr, flags, p.tiles_m, p.tiles_n, p.full, p.S16, slabs, p.finish ? nullptr : cnt, aux0, aux1, aux_ld, aux_n, p.sk,
+                           NoGroup{});
+        if (p.finish) {
             // one wave per workgroup, except for the sum of squares (all R16 waves of a tile half in one block: fixed-order reduction)
-#define FIN_ARGS 0, s, C, M, N, ldc, bias, res, ldr, flags, tiles_m, tiles_n, full, S16, slabs, aux0, aux1, aux_ld, aux_n, plan.units, nk
-            bool done = false;
+#define FIN_ARGS 0, s, C, M, N, ldc, bias, res, ldr, flags, p.tiles_m, p.tiles_n, p.full, p.S16, slabs, aux0, aux1, aux_ld, aux_n, p.sk.units, p.nk
             if constexpr (!SWIGLU && PAIR == PAIR_NONE) {
                 if (flags & EPI_SUMSQ) {
-                    MANTIS_LAUNCH((gemm_ring16_finish_kernel<R16, (AKM || BKM), false, PAIR_NONE, R16>), dim3(rem * 2), dim3(R16 * 64), FIN_ARGS);
-                    done = true;
+                    MANTIS_LAUNCH((gemm_ring16_finish_kernel<R16, (AKM || BKM), false, PAIR_NONE, R16>), dim3(p.rem * 2), dim3(R16 * 64), FIN_ARGS);
+                    return mantis_check_launch();
                 }
             }
-            if (!done)
-                MANTIS_LAUNCH((gemm_ring16_finish_kernel<R16, (AKM || BKM), SWIGLU, PAIR, 1>), dim3(rem * 2 * R16), dim3(64), FIN_ARGS);
+            MANTIS_LAUNCH((gemm_ring16_finish_kernel<R16, (AKM || BKM), SWIGLU, PAIR, 1>), dim3(p.rem * 2 * R16), dim3(64), FIN_ARGS);
 #undef FIN_ARGS
         }
     } else {
-        MANTIS_LAUNCH((gemm_nt_ring_kernel<AKM, BKM, SWIGLU>), dim3(grid), dim3(512), 0, s, A, B, C, M, N, K, lda, ldb, ldc, bias, res, ldr, flags,
-                           tiles_m, tiles_n, full, S, slabs, cnt);
+        MANTIS_LAUNCH((gemm_nt_ring_kernel<AKM, BKM, SWIGLU>), dim3(p.grid), dim3(512), 0, s, A, B, C, M, N, K, lda, ldb, ldc, bias, res, ldr, flags,
+                           p.tiles_m, p.tiles_n, p.full, p.S, slabs, cnt);
     }
     return mantis_check_launch();
 }
-
-// ---- the 176-row kernel: launcher and planner
-// (gemm176.hip)
+// the 256 x 256 ring kernel of `variant`: 12 (plain epilogues only), 13 or 14; a = launch_gemm_ring's arguments
+template <bool AKM, bool BKM, bool SWIGLU = false, int PAIR = PAIR_NONE, class... T>
+static int launch_ring_variant(int variant, T... a) {
+    if (variant == 13) return launch_gemm_ring<AKM, BKM, SWIGLU, 4, PAIR>(a...);
+    if constexpr (PAIR == PAIR_NONE) { if (variant == 12) return launch_gemm_ring<AKM, BKM, SWIGLU, 0>(a...); }
+    return launch_gemm_ring<AKM, BKM, SWIGLU, 8, PAIR>(a...);
+}
+// the 176-row kernel (gemm176.hip)
 int mantis_launch_ring176(hipStream_t s, const bf16_t* A, const bf16_t* B, bf16_t* C, int M, int N, int K, long lda, long ldb, long ldc,
                           const bf16_t* bias, const bf16_t* res, long ldr, int flags, int bkm, int kind, int cus, bf16_t* aux0, const bf16_t* aux1,
                           long aux_ld, int aux_n);
-// MANTIS_GEMM_176 (read once): 0 = never, 1 = where the planner predicts a gain (default), 2 = wherever the kernel applies (A/B measurements)
-static int ring176_mode() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MANTIS_GEMM_176"); v = (e && e[0] >= '0' && e[0] <= '2' && e[1] == 0) ? e[0] - '0' : 1; }
-    return v;
-}
-// Predicted launch time (us) of the two tilings, per CU: rounds x (K-steps x loop time + fixed cost per tile).  256 x 256: the cost model of
-// gemm_pick_variant (1.45 us per K-step, 5 K-step equivalents of prologue + epilogue per round, the K-split remainder round and its reduction);
-// 176 x 256: R176_STEP_US per K-step (measured, profiles/r06_gemm_176.md) and the same fixed cost, whole tiles only.
-#ifndef R176_STEP_US
-#define R176_STEP_US 1.02
-#endif
-#ifndef R176_FIXED_US
-#define R176_FIXED_US 7.5
-#endif
-static bool ring176_wins(int M, int N, int K, int cus_req) {
-    const int mode = ring176_mode();
-    if (mode == 0 || M < 176 * 2 || N < 256) return false;
-    if (mode == 2) return true;
-    const int cus = plan_cus(cus_req), nk = cdiv(K, BK);
-    const long t256 = (long)cdiv(M, 256) * cdiv(N, 256), t176 = (long)cdiv(M, 176) * cdiv(N, 256);
-    const int S = ring_split(t256, nk, cus);
-    const long rem = t256 % cus;
-    const int sub = rem ? (int)((S * rem + cus - 1) / cus) : 0;
-    const double us256 = 1.45 * ((double)(t256 / cus) * (nk + 5.0) + (rem ? sub * ((double)nk / S + 5.0) + (S > 1 ? 8.0 + 1.7 * S : 0.0) : 0.0));
-    const double us176 = (double)((t176 + cus - 1) / cus) * (nk * R176_STEP_US + R176_FIXED_US);
-    return us176 < 0.97 * us256;
-}
 
-// which ring kernel the automatic choice takes (read once): MANTIS_GEMM_RING = 12 (8 waves, 32x32x16), 13 (4 waves x 128x128, 16x16x32) or
-// 14 (8 waves x 128x64, 16x16x32) -- A/B measurements; the default is the measured per-shape choice of ring_variant_for()
-static int default_ring_variant() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("MANTIS_GEMM_RING");
-        v = (e && e[0] == '1' && e[1] >= '2' && e[1] <= '4' && e[2] == 0) ? 10 + (e[1] - '0') : 0;
-    }
-    return v;
-}
+// the operands of an entry point as the launchers take them, and its launch for each layout
+#define OPERANDS (hipStream_t)stream, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, M, N, K, (long)lda, (long)ldb, (long)ldc
+#define BY_LAYOUT(L) (akm && bkm ? L(true, true) : bkm ? L(false, true) : akm ? L(true, false) : L(false, false))
 
 extern "C" {
 
@@ -1452,155 +1257,44 @@ int mantis_probe_ring16_stamps(void* host_dst, int n_wg) {
 #endif
 
 // tile variant the auto heuristic picks for C[M,N] over K (12 = 256x256 ring kernel, 1 = 128x128 generic kernel)
-int mantis_gemm_pick_variant(int M, int N, int K) { return gemm_pick_variant(M, N, K); }
+int mantis_gemm_pick_variant(int M, int N, int K) { return gemm_pick_variant(M, N, K, budget(0)); }
 // the same for a launch planned for `cus` compute units (bits 16-27 of its flags); cus <= 0: the default budget
-int mantis_gemm_pick_variant_cus(int M, int N, int K, int cus) { return gemm_pick_variant(M, N, K, cus > 0 ? cus : 0); }
+int mantis_gemm_pick_variant_cus(int M, int N, int K, int cus) { return gemm_pick_variant(M, N, K, budget(cus)); }
 
-// The remainder-round plan of a ring16 launch of C[M,N] over K planned for `cus` compute units (<= 0: the default budget), as the launcher and
-// the kernels compute it -- for tests and tools, no device work.  out[0..7] = {tiles, full, remainder tiles, S (equal split; 1 = no split),
-// balanced units (0 = equal split), tail slots, remainder workgroups in the grid, K-steps}; then, while they fit `cap` ints, one record of 4
-// ints per remainder workgroup in grid order: {remainder tile (-1: an empty tail slot), first K-step, end K-step, slab}.  Returns the number of
-// ints the full description has.  (The records restate the kernel's own arithmetic, gemm_nt_ring16_kernel: the same sk_bound.)
-int mantis_gemm_remainder_plan(int M, int N, int K, int cus_req, int* out, int cap) {
-    if (M <= 0 || N <= 0 || K <= 0 || !out || cap < 8) return MANTIS_EINVAL;
-    const int tiles_m = cdiv(M, 256), tiles_n = cdiv(N, 256), nk = cdiv(K, BK);
-    const long ntiles = (long)tiles_m * tiles_n;
-    const int cus = plan_cus(cus_req > 0 ? cus_req : 0);
-    const int rem = (int)(ntiles % cus);
-    const int S = ring_split(ntiles, nk, cus);
-    const int full = S > 1 ? (int)(ntiles - rem) : (int)ntiles;
-    SkPlan plan;
-    plan.units = 0;
-    plan.nspan = 0;
-    if (S > 1 && sk_finish_enabled()) sk_make_plan(plan, rem, S, nk, cus);
-    const int nwg = S > 1 ? (plan.units ? plan.units + plan.nspan : S * rem) : 0;
-    const int head[8] = {(int)ntiles, full, S > 1 ? rem : 0, S, plan.units, plan.nspan, nwg, nk};
-    for (int i = 0; i < 8; ++i) out[i] = head[i];
-    int n = 8;
-    for (int j = 0; j < nwg; ++j, n += 4) {
-        int rec[4];
-        if (plan.units == 0) {
-            const int nu = nwg, q = nu >> 3, r = nu & 7, xcd = j & 7;
-            const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (j >> 3);
-            const int part = lin / rem, tl = lin - part * rem;
-            rec[0] = tl;
-            rec[1] = (int)((unsigned)nk * (unsigned)part / (unsigned)S);
-            rec[2] = (int)((unsigned)nk * (unsigned)(part + 1) / (unsigned)S);
-            rec[3] = tl * S + part;
-        } else {
-            const int U = plan.units, T = rem * nk;
-            const bool first = j < U;
-            const int c = first ? j : (int)plan.span[j - U];
-            if (c == (int)SK_EMPTY) {
-                rec[0] = -1; rec[1] = rec[2] = rec[3] = 0;
-            } else {
-                const int a0 = sk_bound(c, U, T, nk), a1 = sk_bound(c + 1, U, T, nk);
-                int tl = a0 / nk;
-                if (first) {
-                    const int e = (tl + 1) * nk;
-                    rec[0] = tl; rec[1] = a0 - tl * nk; rec[2] = (a1 < e ? a1 : e) - tl * nk; rec[3] = c;
-                } else {
-                    tl += 1;
-                    rec[0] = tl; rec[1] = 0; rec[2] = a1 - tl * nk; rec[3] = U + tl - 1;
-                }
-            }
-        }
-        if (n + 4 <= cap) for (int i = 0; i < 4; ++i) out[n + i] = rec[i];
-    }
-    return n;
-}
+// The remainder-round plan of a ring16 launch of C[M,N] over K planned for `cus` compute units (<= 0: the default budget), as the launcher
+// computes it -- for tests and tools, no device work.  out[0..7] = {tiles, full, remainder tiles, S (equal split; 1 = no split), balanced units
+// (0 = equal split), tail slots, remainder workgroups in the grid, K-steps}; then, while they fit `cap` ints, one record of 4 ints per remainder
+// workgroup in grid order: {remainder tile (-1: an empty tail slot), first K-step, end K-step, slab}.  Returns the number of ints the full
+// description has.
+int mantis_gemm_remainder_plan(int M, int N, int K, int cus_req, int* out, int cap) { return gemm_remainder_plan(M, N, K, budget(cus_req), out, cap); }
+
+// Bytes of caller-owned, 256-B aligned, ZERO-INITIALISED device workspace the launch of C[M,N] over K needs (0 = none): only the
+// 256x256 ring kernel's split-K remainder round uses it.  M = N = K = 0 returns the largest requirement of any shape on this
+// device, so a caller can allocate one buffer per stream up front (launches sharing a workspace must be stream-ordered).
+int mantis_gemm_workspace_bytes(int M, int N, int K) { return gemm_workspace_bytes(M, N, K, num_cus()); }
+
+// CU budget a launch plans for when it asks for `cus` (bits 16-27 of its flags): cus > 0 -> clamped to [8, #CU]; cus <= 0 -> the default
+// (MANTIS_GEMM_CUS, else the whole device).  A pure query: there is no process-wide budget to set any more (round 5).
+int mantis_gemm_cu_budget(int cus) { return budget(cus); }
 
 // C[M,N] (bf16, row stride ldc) = epilogue(A[M,K] . B[N,K]^T); A,B,C 16-B aligned, lda/ldb % 8 == 0, K % 8 == 0.
 // flags: bit0 bias[n] add | bits1-3 activation (1 gelu-erf, 2 gelu-tanh, 3 quick-gelu) | bit4 + residual[m,n] (stride ldr)
 //        | bit5 accumulate into C (C += result, used for gradient accumulation) | bits8-11 tile variant (0 = auto)
-// Bytes of caller-owned, 256-B aligned, ZERO-INITIALISED device workspace the launch of C[M,N] over K needs (0 = none): only the
-// 256x256 ring kernel's split-K remainder round uses it.  M = N = K = 0 returns the largest requirement of any shape on this
-// device, so a caller can allocate one buffer per stream up front (launches sharing a workspace must be stream-ordered).
-int mantis_gemm_workspace_bytes(int M, int N, int K) {
-    const int cus = num_cus();
-    if (M <= 0 && N <= 0 && K <= 0) return (int)sk_ws_bytes(cus);
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    const long t256 = (long)cdiv(M, 256) * cdiv(N, 256);
-    return ring_split(t256, cdiv(K, BK), plan_cus(0)) > 1 ? (int)sk_ws_bytes(cus) : 0;
-}
-
-// CU budget a launch plans for when it asks for `cus` (bits 16-27 of its flags): cus > 0 -> clamped to [8, #CU]; cus <= 0 -> the default
-// (MANTIS_GEMM_CUS, else the whole device).  A pure query: there is no process-wide budget to set any more (round 5).
-int mantis_gemm_cu_budget(int cus) { return plan_cus(cus > 0 ? cus : 0); }
-
 int mantis_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int M, int N, int K,
                         const void* bias, const void* residual, int64_t ldr, int flags, void* workspace, int64_t workspace_bytes,
                         void* stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || (flags & EPI_SUMSQ)) return MANTIS_EINVAL;      // bit 7 belongs to mantis_gemm_bf16_nt_sumsq
+    const GemmChoice c = gemm_nt_choose(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, flags, num_cus());
+    if (c.rc) return c.rc;
     const bool akm = flags & EPI_A_KMAJOR, bkm = flags & EPI_B_KMAJOR;
-    if (lda % 8 || ldb % 8 || ldc < N) return MANTIS_EUNSUPPORTED;
-    const int K8 = (K + 7) / 8 * 8;
-    if ((!akm && lda < K8) || (!bkm && ldb < K8) || (akm && lda < M) || (bkm && ldb < N)) return MANTIS_EUNSUPPORTED;
-    // row-major operands are fetched in whole 16-B chunks along K: with K % 8 != 0 the tail chunk must meet zeros on the other
-    // side, which only a K-major operand (rows k >= K come from the zero page) guarantees; the row-major pad must be finite
-    if (!akm && !bkm && (K % 8)) return MANTIS_EUNSUPPORTED;
-    if (((uintptr_t)A | (uintptr_t)B) & 15) return MANTIS_EUNSUPPORTED;
-    if ((flags & EPI_BIAS) && !bias) return MANTIS_EINVAL;
-    if ((flags & EPI_RESIDUAL) && !residual) return MANTIS_EINVAL;
-    if (flags & EPI_SWIGLU_BWD) {      // residual = [gate | up], C = [dgate | dup], both [M, 2N]; only the ring kernel's epilogue has it
-        if (!residual || (flags & (EPI_BIAS | EPI_ACT_MASK | EPI_RESIDUAL | EPI_ACCUM)) || ldc < 2 * (long)N || ldr < 2 * (long)N)
-            return MANTIS_EINVAL;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    int variant = (flags & EPI_VARIANT_MASK) >> EPI_VARIANT_SHIFT;
-    // variant 12 = the 8-wave ring kernel (32x32x16 MFMA), 13 / 14 = the ring16 kernel (16x16x32 MFMA) with 4 / 8 waves: same tile, same
-    // work split, same results up to the accumulation order inside a K-step
-    if (variant == 0) {
-        variant = (flags & EPI_SWIGLU_BWD) ? 12 : gemm_pick_variant(M, N, K, flags_cus(flags));
-        if (variant == 12) {
-            variant = default_ring_variant() ? default_ring_variant() : ring_variant_for(M, N, K, akm, bkm, flags_cus(flags));
-            // the 176-row tile where it turns the grid into whole rounds (A row-major: forward and dX)
-            if (!default_ring_variant() && !akm && ring176_wins(M, N, K, flags_cus(flags))) variant = 15;
-        }
-    }
-    const bool r176 = variant == 15;
-    const bool ring = variant >= 12 && variant <= 15, big = variant == 2;
-    if (r176 && akm) return MANTIS_EUNSUPPORTED;               // the M side is row-major in the 176-row kernel
-    if ((flags & EPI_SWIGLU_BWD) && (!ring || akm || !bkm)) return MANTIS_EUNSUPPORTED;
-    // the ring kernels address their operands through buffer descriptors: unsigned 32-bit num_records, unsigned 32-bit lane offset and
-    // unsigned 32-bit scalar K-step offset (the hardware adds them to the 48-bit base without wrapping).  An operand of 4 GiB or more
-    // would wrap silently -> such shapes go to the generic kernel (64-bit addresses) when the choice is ours, and are refused when a
-    // ring kernel was asked for explicitly.  (The first guard stood at 2 GiB; the lm_head logits of 8192 rows x 152064 columns, 2.5 GB,
-    // then fell to the generic kernel at 0.34 PFLOP/s.  `gemm_operand_over_2gib` checks the 2-4 GiB range against the generic kernel.)
-    if (ring) {
-        const long a_bytes = (long)(akm ? K : M) * (long)lda * 2, b_bytes = (long)(bkm ? K : N) * (long)ldb * 2;
-        const long lim = (1L << 32) - (1L << 16);
-        if (a_bytes >= lim || b_bytes >= lim) {
-            if ((flags & EPI_VARIANT_MASK) || (flags & EPI_SWIGLU_BWD)) return MANTIS_EUNSUPPORTED;
-            variant = 1;
-            return mantis_gemm_bf16_nt(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, flags | (1 << EPI_VARIANT_SHIFT), workspace,
-                                       workspace_bytes, stream);
-        }
-    }
-#define GEMM_ARGS s, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, M, N, K, (long)lda, (long)ldb, (long)ldc, \
-                  (const bf16_t*)bias, (const bf16_t*)residual, (long)ldr, flags
-#define RING_ARGS GEMM_ARGS, workspace, (long)workspace_bytes
-    // variant 1 = 128x128 generic kernel, 2 = 256x256 generic kernel, 12 / 13 = 256x256 ring kernels (default for well-quantised shapes)
-    if (!ring && !big && variant != 1) return MANTIS_EINVAL;
-    if (r176) {
-        return mantis_launch_ring176(GEMM_ARGS, bkm ? 1 : 0, 0, plan_cus(flags_cus(flags)), nullptr, nullptr, 0L, 0);
-    }
-#define RING_DISPATCH(AK, BK_, SW) (variant == 13 ? launch_gemm_ring<AK, BK_, SW, 4>(RING_ARGS) \
-                                    : variant == 14 ? launch_gemm_ring<AK, BK_, SW, 8>(RING_ARGS) : launch_gemm_ring<AK, BK_, SW, 0>(RING_ARGS))
-    if (akm && bkm)
-        return ring ? RING_DISPATCH(true, true, false)
-                    : big ? launch_gemm<256, 256, 128, 64, true, true>(GEMM_ARGS) : launch_gemm<128, 128, 64, 64, true, true>(GEMM_ARGS);
-    if (flags & EPI_SWIGLU_BWD) return RING_DISPATCH(false, true, true);
-    if (bkm)
-        return ring ? RING_DISPATCH(false, true, false)
-                    : big ? launch_gemm<256, 256, 128, 64, false, true>(GEMM_ARGS) : launch_gemm<128, 128, 64, 64, false, true>(GEMM_ARGS);
-    if (akm)
-        return ring ? RING_DISPATCH(true, false, false)
-                    : big ? launch_gemm<256, 256, 128, 64, true, false>(GEMM_ARGS) : launch_gemm<128, 128, 64, 64, true, false>(GEMM_ARGS);
-    return ring ? RING_DISPATCH(false, false, false)
-                : big ? launch_gemm<256, 256, 128, 64, false, false>(GEMM_ARGS) : launch_gemm<128, 128, 64, 64, false, false>(GEMM_ARGS);
-#undef RING_DISPATCH
-#undef RING_ARGS
+#define GEMM_ARGS OPERANDS, (const bf16_t*)bias, (const bf16_t*)residual, (long)ldr, c.flags
+#define RING_L(AK, BK_) launch_ring_variant<AK, BK_>(c.variant, GEMM_ARGS, workspace, (long)workspace_bytes)
+#define GENERIC(AK, BK_) (c.variant == 2 ? launch_gemm<256, 256, 128, 64, AK, BK_>(GEMM_ARGS) : launch_gemm<128, 128, 64, 64, AK, BK_>(GEMM_ARGS))
+    if (c.variant == 15) return mantis_launch_ring176(GEMM_ARGS, bkm ? 1 : 0, 0, budget(flags_cus(flags)), nullptr, nullptr, 0L, 0);
+    if (c.variant < 12) return BY_LAYOUT(GENERIC);
+    if (flags & EPI_SWIGLU_BWD) return launch_ring_variant<false, true, true>(c.variant, GEMM_ARGS, workspace, (long)workspace_bytes);
+    return BY_LAYOUT(RING_L);
+#undef GENERIC
+#undef RING_L
 #undef GEMM_ARGS
 }
 
@@ -1612,59 +1306,13 @@ int mantis_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64_t ldb, 
 // no bias / activation / residual; anything else returns MANTIS_EUNSUPPORTED and the caller runs mantis_gemm_bf16_nt + mantis_sumsq.
 int mantis_gemm_bf16_nt_sumsq(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int M, int N, int K, int flags,
                               float* tile_sumsq, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || !tile_sumsq) return MANTIS_EINVAL;
-    if (flags & ~(EPI_ACCUM | EPI_A_KMAJOR | EPI_B_KMAJOR | EPI_VARIANT_MASK | EPI_SK_INKERNEL | EPI_CUS_MASK)) return MANTIS_EUNSUPPORTED;
+    const GemmChoice c = gemm_sumsq_choose(A, lda, B, ldb, C, ldc, M, N, K, flags, tile_sumsq, num_cus());
+    if (c.rc) return c.rc;
     const bool akm = flags & EPI_A_KMAJOR, bkm = flags & EPI_B_KMAJOR;
-    if (N % 256 || ldc % 8 || ldc < N || lda % 8 || ldb % 8 || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15)) return MANTIS_EUNSUPPORTED;
-    const int K8 = (K + 7) / 8 * 8;
-    if ((!akm && lda < K8) || (!bkm && ldb < K8) || (akm && lda < M) || (bkm && ldb < N) || (!akm && !bkm && (K % 8))) return MANTIS_EUNSUPPORTED;
-    const long a_bytes = (long)(akm ? K : M) * (long)lda * 2, b_bytes = (long)(bkm ? K : N) * (long)ldb * 2, lim = (1L << 32) - (1L << 16);
-    if (a_bytes >= lim || b_bytes >= lim) return MANTIS_EUNSUPPORTED;
-    int variant = (flags & EPI_VARIANT_MASK) >> EPI_VARIANT_SHIFT;
-    if (variant == 0) {
-        if (gemm_pick_variant(M, N, K, flags_cus(flags)) != 12) return MANTIS_EUNSUPPORTED;
-        variant = default_ring_variant() >= 13 ? default_ring_variant() : ring_variant_for(M, N, K, akm, bkm, flags_cus(flags));
-    }
-    if (variant != 13 && variant != 14) return MANTIS_EUNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const int f = (flags & ~EPI_VARIANT_MASK) | EPI_SUMSQ;
-#define SS_ARGS s, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, M, N, K, (long)lda, (long)ldb, (long)ldc, (const bf16_t*)nullptr, \
-                (const bf16_t*)nullptr, 0L, f, workspace, (long)workspace_bytes, (bf16_t*)tile_sumsq, (const bf16_t*)nullptr, 0L, 0
-#define SS_DISPATCH(AK, BK_) (variant == 13 ? launch_gemm_ring<AK, BK_, false, 4>(SS_ARGS) : launch_gemm_ring<AK, BK_, false, 8>(SS_ARGS))
-    if (akm && bkm) return SS_DISPATCH(true, true);
-    if (bkm) return SS_DISPATCH(false, true);
-    if (akm) return SS_DISPATCH(true, false);
-    return SS_DISPATCH(false, false);
-#undef SS_DISPATCH
-#undef SS_ARGS
-}
-
-// ---- two weight-gradient GEMMs in one grid (see RingGroup2 at the kernel)
-// predicted launch time (us) of C[M,N] over K on the 256 x 256 ring kernels for `cus` CUs, the cost model of gemm_pick_variant
-static double ring256_us(int M, int N, int K, int cus) {
-    const int nk = cdiv(K, BK);
-    const long t = (long)cdiv(M, 256) * cdiv(N, 256);
-    const int S = ring_split(t, nk, cus);
-    const long rem = t % cus;
-    const int sub = rem ? (int)((S * rem + cus - 1) / cus) : 0;
-    return 1.45 * ((double)(t / cus) * (nk + 5.0) + (rem ? sub * ((double)nk / S + 5.0) + (S > 1 ? 8.0 + 1.7 * S : 0.0) : 0.0));
-}
-static bool tn_pair_wins(int M1, int N1, int M2, int N2, int K, int cus_req) {
-    static int mode = -1;              // MANTIS_GEMM_PAIR (read once): 0 never, 1 where the model predicts a gain (default), 2 always
-    if (mode < 0) { const char* e = getenv("MANTIS_GEMM_PAIR"); mode = (e && e[0] >= '0' && e[0] <= '2' && e[1] == 0) ? e[0] - '0' : 1; }
-    if (mode == 0 || default_ring_variant()) return false;
-    if (mode == 2) return true;
-    const int cus = plan_cus(cus_req), nk = cdiv(K, BK);
-    const long t = (long)cdiv(M1, 256) * cdiv(N1, 256) + (long)cdiv(M2, 256) * cdiv(N2, 256);
-    const double both = 1.45 * (double)((t + cus - 1) / cus) * (nk + 5.0);
-    return both < 0.97 * (ring256_us(M1, N1, K, cus) + ring256_us(M2, N2, K, cus));
-}
-static int tn_operand_ok(const void* A, int64_t lda, const void* B, int64_t ldb, const void* C, int64_t ldc, int M, int N, int K) {
-    if (M <= 0 || N <= 0) return MANTIS_EINVAL;
-    if (N % 256 || ldc % 8 || ldc < N || lda % 8 || ldb % 8 || lda < M || ldb < N || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15)) return MANTIS_EUNSUPPORTED;
-    const long lim = (1L << 32) - (1L << 16);
-    if ((long)K * lda * 2 >= lim || (long)K * ldb * 2 >= lim) return MANTIS_EUNSUPPORTED;
-    return 0;
+#define SUMSQ(AK, BK_) launch_ring_variant<AK, BK_>(c.variant, OPERANDS, (const bf16_t*)nullptr, (const bf16_t*)nullptr, 0L, c.flags, workspace, \
+                                                    (long)workspace_bytes, (bf16_t*)tile_sumsq, (const bf16_t*)nullptr, 0L, 0)
+    return BY_LAYOUT(SUMSQ);
+#undef SUMSQ
 }
 
 // 1 when mantis_gemm_bf16_tn_pair would run C1[M1,N1] and C2[M2,N2] (both over K, both operands K-major) as ONE grid and the cost model
@@ -1672,23 +1320,19 @@ static int tn_operand_ok(const void* A, int64_t lda, const void* B, int64_t ldb,
 // Mistral-7B layer: 896 + 384 tiles = 5.0 rounds on 256 CUs; 0 otherwise.  A pure query.
 int mantis_gemm_tn_pair_wins(int M1, int N1, int M2, int N2, int K, int cus) {
     if (M1 <= 0 || N1 <= 0 || M2 <= 0 || N2 <= 0 || K <= 0 || N1 % 256 || N2 % 256) return 0;
-    return tn_pair_wins(M1, N1, M2, N2, K, cus > 0 ? cus : 0) ? 1 : 0;
+    return tn_pair_wins(M1, N1, M2, N2, K, budget(cus)) ? 1 : 0;
 }
-// Two weight-gradient GEMMs in ONE launch: C1 (+)= A1^T-view . B1 and C2 (+)= A2^T-view . B2, i.e. mantis_gemm_bf16_nt_sumsq's TN form
-// (A given [K, M], B given [K, N]; flags: 32 accumulate | bits 16-27 CU budget) for two problems that share K.  ts1 / ts2: per 256 x 256 tile
-// sums of squares of what was stored (cdiv(M,256) * cdiv(N,256) floats each), or both NULL for none.  Whole tiles of the 8-wave ring16 kernel
-// in one XCD-contiguous order over the union of the two grids: no K split, no workspace.  Each result is bit-identical to the one
-// mantis_gemm_bf16_nt(_sumsq) writes with variant 14 for a shape WITHOUT a K-split remainder (same kernel code, whole tiles); against a
-// K-split launch of the same shape the fp32 summation order of the remainder tiles differs (bf16 rounding).  MANTIS_EUNSUPPORTED: N % 256, unaligned
-// operands, >= 4 GiB operands.
+// Two weight-gradient GEMMs in ONE launch (see RingGroup2 at the kernel): C1 (+)= A1^T-view . B1 and C2 (+)= A2^T-view . B2, i.e.
+// mantis_gemm_bf16_nt_sumsq's TN form (A given [K, M], B given [K, N]; flags: 32 accumulate | bits 16-27 CU budget) for two problems that share K.
+// ts1 / ts2: per 256 x 256 tile sums of squares of what was stored (cdiv(M,256) * cdiv(N,256) floats each), or both NULL for none.  Whole tiles
+// of the 8-wave ring16 kernel in one XCD-contiguous order over the union of the two grids: no K split, no workspace.  Each result is
+// bit-identical to the one mantis_gemm_bf16_nt(_sumsq) writes with variant 14 for a shape WITHOUT a K-split remainder (same kernel code, whole
+// tiles); against a K-split launch of the same shape the fp32 summation order of the remainder tiles differs (bf16 rounding).
+// MANTIS_EUNSUPPORTED: N % 256, unaligned operands, >= 4 GiB operands.
 int mantis_gemm_bf16_tn_pair(const void* A1, int64_t lda1, const void* B1, int64_t ldb1, void* C1, int64_t ldc1, int M1, int N1, float* ts1,
                              const void* A2, int64_t lda2, const void* B2, int64_t ldb2, void* C2, int64_t ldc2, int M2, int N2, float* ts2,
                              int K, int flags, void* stream) {
-    if (K <= 0 || (ts1 == nullptr) != (ts2 == nullptr)) return MANTIS_EINVAL;
-    if (flags & ~(EPI_ACCUM | EPI_CUS_MASK)) return MANTIS_EUNSUPPORTED;
-    int rc = tn_operand_ok(A1, lda1, B1, ldb1, C1, ldc1, M1, N1, K);
-    if (rc == 0) rc = tn_operand_ok(A2, lda2, B2, ldb2, C2, ldc2, M2, N2, K);
-    if (rc != 0) return rc;
+    if (const int rc = gemm_pair_check(A1, lda1, B1, ldb1, C1, ldc1, M1, N1, ts1, A2, lda2, B2, ldb2, C2, ldc2, M2, N2, ts2, K, flags)) return rc;
     RingGroup2 g;
     g.A = (const bf16_t*)A2; g.B = (const bf16_t*)B2; g.C = (bf16_t*)C2; g.aux0 = (bf16_t*)ts2;
     g.lda = (long)lda2; g.ldb = (long)ldb2; g.ldc = (long)ldc2;
@@ -1697,8 +1341,7 @@ int mantis_gemm_bf16_tn_pair(const void* A1, int64_t lda1, const void* B1, int64
     g.tiles1 = tm1 * tn1;
     const int total = g.tiles1 + g.tiles_m * g.tiles_n;
     SkPlan plan;
-    plan.units = 0;
-    plan.nspan = 0;
+    plan.units = plan.nspan = 0;
     const int f = (flags & EPI_ACCUM) | EPI_A_KMAJOR | EPI_B_KMAJOR | (ts1 ? EPI_SUMSQ : 0);
     MANTIS_LAUNCH((gemm_nt_ring16_kernel<8, true, true, false, PAIR_NONE, RingGroup2>), dim3(total), dim3(512), 0, (hipStream_t)stream,
                        (const bf16_t*)A1, (const bf16_t*)B1, (bf16_t*)C1, M1, N1, K, (long)lda1, (long)ldb1, (long)ldc1, (const bf16_t*)nullptr,
@@ -1717,39 +1360,15 @@ int mantis_gemm_bf16_tn_pair(const void* A1, int64_t lda1, const void* B1, int64
 int mantis_gemm_bf16_nt_fused(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int M, int N, int K,
                               const void* bias, int mode, void* aux0, const void* aux1, int64_t aux_ld, int aux_n, int variant,
                               void* workspace, int64_t workspace_bytes, void* stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || (mode != PAIR_SWIGLU && mode != PAIR_ROPE) || !aux0) return MANTIS_EINVAL;
-    if (lda % 8 || ldb % 8 || ldc % 8 || ldc < N || lda < K || ldb < K || K % 8 || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15))
-        return MANTIS_EUNSUPPORTED;
-    if (aux_ld % 8 || ((uintptr_t)aux0 & 15)) return MANTIS_EUNSUPPORTED;
-    if (mode == PAIR_SWIGLU && (N % 256 || aux_ld < N / 2 || bias)) return MANTIS_EUNSUPPORTED;
-    if (mode == PAIR_ROPE && (N % 256 || aux_n % 128 || aux_n > N || aux_n < 0 || !aux1 || aux_ld < 64 || ((uintptr_t)aux1 & 15)))
-        return MANTIS_EUNSUPPORTED;
-    const long lim = (1L << 32) - (1L << 16);
-    if ((long)M * lda * 2 >= lim || (long)N * ldb * 2 >= lim) return MANTIS_EUNSUPPORTED;
-    const bool inkernel = variant & 64;          // bit 6 of `variant`: see EPI_SK_INKERNEL
-    const bool shared = variant & 128;           // bit 7 of `variant`: see EPI_SHARED_GPU
-    const int cus_bits = variant & EPI_CUS_MASK; // bits 16-27 of `variant`: the CU budget, as in mantis_gemm_bf16_nt's flags
-    variant &= 15;
-    if (variant == 0) {
-        variant = default_ring_variant() >= 13 ? default_ring_variant() : ring_variant_for(M, N, K, false, false, cus_bits >> EPI_CUS_SHIFT);
-        if (default_ring_variant() < 13 && ring176_wins(M, N, K, cus_bits >> EPI_CUS_SHIFT)) variant = 15;
-    }
-    if (variant < 13 || variant > 15) return MANTIS_EUNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const int flags = (bias ? EPI_BIAS : 0) | (inkernel ? EPI_SK_INKERNEL : 0) | (shared ? EPI_SHARED_GPU : 0) | cus_bits;
-#define PAIR_ARGS s, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, M, N, K, (long)lda, (long)ldb, (long)ldc, (const bf16_t*)bias, \
-                  (const bf16_t*)nullptr, 0L, flags, workspace, (long)workspace_bytes, (bf16_t*)aux0, (const bf16_t*)aux1, (long)aux_ld, aux_n
-    if (variant == 15) {
-        return mantis_launch_ring176(s, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, M, N, K, (long)lda, (long)ldb, (long)ldc, (const bf16_t*)bias,
-                                     (const bf16_t*)nullptr, 0L, flags, 0, mode, plan_cus(cus_bits >> EPI_CUS_SHIFT), (bf16_t*)aux0,
-                                     (const bf16_t*)aux1, (long)aux_ld, aux_n);
-    }
-    if (mode == PAIR_SWIGLU)
-        return variant == 13 ? launch_gemm_ring<false, false, false, 4, PAIR_SWIGLU>(PAIR_ARGS)
-                             : launch_gemm_ring<false, false, false, 8, PAIR_SWIGLU>(PAIR_ARGS);
-    return variant == 13 ? launch_gemm_ring<false, false, false, 4, PAIR_ROPE>(PAIR_ARGS)
-                         : launch_gemm_ring<false, false, false, 8, PAIR_ROPE>(PAIR_ARGS);
-#undef PAIR_ARGS
+    const GemmChoice c = gemm_fused_choose(A, lda, B, ldb, C, ldc, M, N, K, bias, mode, aux0, aux1, aux_ld, aux_n, variant, num_cus());
+    if (c.rc) return c.rc;
+#define FUSED_ARGS OPERANDS, (const bf16_t*)bias, (const bf16_t*)nullptr, 0L, c.flags
+#define AUX_ARGS (bf16_t*)aux0, (const bf16_t*)aux1, (long)aux_ld, aux_n
+    if (c.variant == 15) return mantis_launch_ring176(FUSED_ARGS, 0, mode, budget(flags_cus(c.flags)), AUX_ARGS);
+    if (mode == PAIR_SWIGLU) return launch_ring_variant<false, false, false, PAIR_SWIGLU>(c.variant, FUSED_ARGS, workspace, (long)workspace_bytes, AUX_ARGS);
+    return launch_ring_variant<false, false, false, PAIR_ROPE>(c.variant, FUSED_ARGS, workspace, (long)workspace_bytes, AUX_ARGS);
+#undef AUX_ARGS
+#undef FUSED_ARGS
 }
 
 }  // extern "C"

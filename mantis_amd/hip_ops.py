@@ -258,7 +258,7 @@ def linear_fwd(x, w, bias=None, act=None, residual=None):
 
 
 def _prefers_256(M, N, K):
-    """True when the library's tile heuristic (csrc/gemm.hip, gemm_pick_variant) takes the 256x256 ring kernel (for the CU budget the
+    """True when the library's tile heuristic (csrc/gemm_plan.h, gemm_pick_variant) takes the 256x256 ring kernel (for the CU budget the
     launch will carry)."""
     return _L.mantis_gemm_pick_variant_cus(M, N, K, _launch().gemm_cus) == 12
 
@@ -389,7 +389,7 @@ def linear_dw(dy, x, grad_w, accumulate):
 
 def dw_pair_wins(out1, in1, out2, in2, tokens):
     """True when linear_dw_pair(...) would run the two weight-gradient GEMMs grad[out1, in1] and grad[out2, in2] over `tokens` rows as ONE grid
-    and the library's cost model predicts a gain over two launches for this context's CU budget (csrc/gemm.hip: tn_pair_wins)."""
+    and the library's cost model predicts a gain over two launches for this context's CU budget (csrc/gemm_plan.h: tn_pair_wins)."""
     return bool(_L.mantis_gemm_tn_pair_wins(int(out1), int(in1), int(out2), int(in2), int(tokens), _launch().gemm_cus))
 
 

@@ -3,7 +3,9 @@
   1. every attention kernel that exists in the base revision's attn.hip / attn_fwd64.hip compiles to the SAME instructions from this tree
      (device code of both sources compiled with the build's flags, disassembled per kernel symbol, addresses stripped);
   2. every *_win_kernel: registers, scratch and spills from -Rpass-analysis=kernel-resource-usage -- no scratch, no VGPR spill.
-`python tools/attn_window_audit.py [BASE_REV]`  (default HEAD~1; give the revision before the window kernels)"""
+`python tools/attn_window_audit.py [BASE_REV] [--sources gemm,gemm176]`  (default HEAD~1; give the revision before the window kernels).
+With --sources the same comparison runs over other translation units -- a refactor that must not move an instruction -- and step 2 becomes:
+every kernel's register, AGPR, scratch and spill figures equal the base revision's."""
 import hashlib
 import os
 import re
@@ -39,7 +41,12 @@ def kernels(elf):
             cur = m.group(1)
             res[cur] = []
         elif cur and line.strip():
-            res[cur].append(re.sub(r"//.*", "", line).strip())
+            ins = re.sub(r"//.*", "", line).strip()
+            # s_getpc_b64 + s_add_u32 <literal>: the distance from here to a function or table elsewhere in the code object -- an address, which
+            # moves with the order the kernels are emitted in, not an instruction
+            if res[cur] and res[cur][-1].startswith("s_getpc_b64") and ins.startswith("s_add_u32"):
+                ins = re.sub(r"0x[0-9a-f]+$", "<pc-relative>", ins)
+            res[cur].append(ins)
     return {k: hashlib.sha1("\n".join(v).encode()).hexdigest() for k, v in res.items()}
 
 
@@ -57,15 +64,21 @@ def resources(log):
 
 
 def main():
-    base = sys.argv[1] if len(sys.argv) > 1 else "HEAD~1"
+    args = sys.argv[1:]
+    sources = SOURCES
+    if "--sources" in args:
+        i = args.index("--sources")
+        sources = tuple(args[i + 1].split(","))
+        del args[i:i + 2]
+    base = args[0] if args else "HEAD~1"
     tmp = tempfile.mkdtemp()
     base_dir = os.path.join(tmp, "base")
     os.makedirs(base_dir)
     arch = subprocess.run(["git", "-C", ROOT, "archive", base, "mantis_amd/csrc"], capture_output=True, check=True).stdout
     subprocess.run(["tar", "-x", "-C", base_dir], input=arch, check=True)
     ok = True
-    for name in SOURCES:
-        b_elf, _ = compile_device(os.path.join(base_dir, "mantis_amd", "csrc"), name, base_dir)
+    for name in sources:
+        b_elf, b_log = compile_device(os.path.join(base_dir, "mantis_amd", "csrc"), name, base_dir)
         n_elf, log = compile_device(os.path.join(ROOT, "mantis_amd", "csrc"), name, tmp)
         b, n = kernels(b_elf), kernels(n_elf)
         same = [k for k in b if n.get(k) == b[k]]
@@ -74,6 +87,14 @@ def main():
         for k in diff:
             print(f"  DIFFERS: {k}")
         ok &= not diff
+        if sources != SOURCES:
+            b_res, n_res = resources(b_log), resources(log)
+            moved = [k for k in b_res if n_res.get(k) != b_res[k]]
+            print(f"  resource usage (VGPRs, AGPRs, scratch, spills, occupancy, LDS): {len(b_res) - len(moved)} kernels unchanged, {len(moved)} changed")
+            for k in moved:
+                print(f"  CHANGED: {k}: {b_res[k]} -> {n_res.get(k)}")
+            ok &= not moved
+            continue
         for k, r in sorted(resources(log).items()):
             if "win_kernel" not in k:
                 continue
