@@ -58,6 +58,7 @@ __global__ __launch_bounds__(CE_THREADS) void ce_fwd_bwd_kernel(bf16_t* __restri
         for (int e = 0; e < 8; ++e)
             if (c * 8 + e < V) cm = fmaxf(cm, f[e]);
         const float nm = fmaxf(m, cm);
+        if (nm == -INFINITY) continue;  // nothing but -inf so far: the chunk adds 0 (__expf(-inf - -inf) is NaN and would outlive the rescale)
         float acc = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e)

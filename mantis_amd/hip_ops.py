@@ -815,15 +815,18 @@ def embed_grad(dmerged, input_ids, plan, grad_weight, accumulate):
     _lib.check(rc, "embed_grad")
 
 
-def ce_fwd_bwd(logits, targets, V, grad_scale, loss_scale, write_grad=True):
+def ce_fwd_bwd(logits, targets, V, grad_scale, loss_scale, write_grad=True, row_lse=None):
     """logits [R, ld>=pad8(V)] bf16 -> overwritten with dlogits; returns (loss[1] fp32, count[2] int32 = [valid rows,
-    rows with an out-of-range target])"""
+    rows with an out-of-range target]).  row_lse (optional fp32 [R] on the device) receives every row's log-sum-exp, 0 on rows
+    without a usable target."""
     R = logits.shape[0]
+    if row_lse is not None and (row_lse.dtype != torch.float32 or row_lse.numel() < R or not row_lse.is_contiguous()):
+        raise ValueError(f"row_lse: expected a contiguous fp32 tensor of at least {R} elements, got {row_lse.dtype} {tuple(row_lse.shape)}")
     ws = torch.empty((R,), dtype=torch.float32, device=logits.device)
     count = torch.empty((2,), dtype=torch.int32, device=logits.device)
     loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
     rc = _L.mantis_ce_fwd_bwd(_p(logits), _p(targets), R, V, logits.stride(0), float(grad_scale), float(loss_scale),
-                              int(write_grad), _p(ws), None, _p(count), _p(loss), _stream())
+                              int(write_grad), _p(ws), _p(row_lse), _p(count), _p(loss), _stream())
     _lib.check(rc, "ce_fwd_bwd")
     return loss, count
 

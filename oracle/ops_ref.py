@@ -505,7 +505,7 @@ def embed_grad(dmerged, input_ids, plan, grad_weight, accumulate):
     grad_weight.copy_(g.to(grad_weight.dtype))
 
 
-def ce_fwd_bwd(logits, targets, V, grad_scale, loss_scale, write_grad=True):
+def ce_fwd_bwd(logits, targets, V, grad_scale, loss_scale, write_grad=True, row_lse=None):
     x = _f(logits)[:, :V]
     t = targets.long()
     valid = (t >= 0) & (t < V)          # t >= V: torch's CrossEntropyLoss raises; the product excludes and reports them
@@ -513,13 +513,15 @@ def ce_fwd_bwd(logits, targets, V, grad_scale, loss_scale, write_grad=True):
     lse = torch.logsumexp(x, dim=-1)
     picked = x.gather(1, t.clamp(min=0, max=V - 1)[:, None])[:, 0]
     row_loss = torch.where(valid, lse - picked, torch.zeros_like(lse))
+    if row_lse is not None:
+        row_lse[: x.shape[0]] = torch.where(valid, lse, torch.zeros_like(lse))
     loss = loss_scale * row_loss.sum() / cnt if cnt else torch.tensor(float("nan"))
     if write_grad:
         g = torch.softmax(x, -1)
         g[torch.arange(x.shape[0])[valid], t[valid]] -= 1.0
         g = g * (grad_scale / cnt if cnt else float("inf"))
         g[~valid] = 0
-        logits.zero_()
+        logits[:, : pad8(V)] = 0          # the kernel writes whole 8-chunks; columns from pad8(V) on are the caller's
         logits[:, :V] = g.to(logits.dtype)
     return loss.reshape(1).float(), torch.tensor([cnt, int((t >= V).sum())], dtype=torch.int32)
 

@@ -369,3 +369,261 @@ class AttnCase:
                 continue
             worst[name] = assert_rowhead(t, self.rows(self.ref, name), heads, self.hd, bars[name][0], f"{what} {name}", count=self.grad_count())
         return worst
+
+
+# ------------------------------------------------------------------------------------------------------------- row-wise kernels
+# norm.hip, ce.hip, rope.hip and the colsum / sumsq / sum_f32 / clip_scale reductions (tests/rowwise_cases.py holds the inputs,
+# tests/test_rowwise_local_error_gpu.py applies the criteria to the kernels, tests/test_local_error_checker.py proves them on the CPU).
+# Every bound has the form
+#       half a bf16 ulp of the float64 reference   (the one rounding of the stored value)
+#     + c . 2^-24 . sum of the |terms| the fp32 value is made of
+# with c the number of fp32 roundings on the longest path to the value: pointwise operations plus the longest chain of additions any term
+# passes through (Higham: a sum evaluated in ANY order errs by at most depth . u . sum |x_i| to first order).  Fused multiply-adds
+# (-ffp-contract=fast) only remove roundings.  Nothing here was fitted to a kernel's output.
+def bf16_round(t64):
+    """float64 -> the nearest bf16 value (ties to even), as float64"""
+    return t64.to(torch.float32).to(torch.bfloat16).to(torch.float64)
+
+
+def half_ulp_bf16(ref64):
+    """half the spacing of bf16 at |ref| (8-bit significand: 2^(e - 8) for 2^e <= |ref| < 2^(e+1)); subnormal spacing below 2^-126"""
+    _, e = torch.frexp(ref64.abs().clamp_min(2.0 ** -126))               # |ref| = m . 2^e, 0.5 <= m < 1
+    return torch.ldexp(torch.ones_like(ref64), e - 9)
+
+
+def as2d(t):
+    return t.reshape(1, -1) if t.dim() < 2 else t.reshape(t.shape[0], -1)
+
+
+def assert_bounded(out, ref64, bound, what, tile=(1, 8)):
+    """assert_elementwise on [rows, cols] (or flat) data with the row-wise kernels' natural tile: one row x one 8-element chunk"""
+    return assert_elementwise(as2d(out), as2d(ref64), as2d(bound), what, tile=tile)
+
+
+def assert_ulp(out, ref64, max_ulp, max_share, what, tile=(1, 8)):
+    """every element of `out` within max_ulp bf16 ulps of the correctly rounded ref64 and at most max_share of them different at all.
+    -> (worst distance, share that differs).  The failure names row and 8-chunk (violation_report)."""
+    d = as2d(ulp_distance_bf16(out, ref64)).to(torch.float64)
+    if d.numel() == 0:
+        return 0, 0.0
+    worst, (r, c), nbad, tiles = violation_report(d / max(max_ulp, 0.5), tile)
+    far = int((d > max_ulp).sum())
+    assert far == 0, (f"{what}: {far} of {d.numel()} elements more than {max_ulp} bf16 ulp from the reference; worst {int(d.max())} ulp at "
+                      f"(row {r}, col {c}); first violating (row, chunk): {tiles}")
+    share = float((d > 0).sum()) / d.numel()
+    rows = sorted(set((d > 0).nonzero()[:, 0].tolist()))[:8]
+    assert share <= max_share, (f"{what}: {share:.3%} of the elements differ from the reference (cap {max_share:.1%}); worst {int(d.max())} "
+                                f"ulp at (row {r}, col {c}); first rows: {rows}")
+    return int(d.max()), share
+
+
+def assert_bit_equal(out, ref, what, tile=(1, 8)):
+    o, r = as2d(out.detach().cpu()), as2d(ref.detach().cpu())
+    assert o.dtype == r.dtype and o.shape == r.shape, f"{what}: {o.dtype} {tuple(o.shape)} vs {r.dtype} {tuple(r.shape)}"
+    ne = o.contiguous().view(torch.int16) != r.contiguous().view(torch.int16) if o.dtype == torch.bfloat16 else (o != r) & ~(o.isnan() & r.isnan())
+    if bool(ne.any()):
+        _, (i, j), nbad, tiles = violation_report(ne.to(torch.float64) * 2.0, tile)
+        raise AssertionError(f"{what}: {nbad} of {ne.numel()} elements not bit-equal, first worst at (row {i}, col {j}): {float(o[i, j])} vs "
+                             f"{float(r[i, j])}; first (row, chunk): {tiles}")
+
+
+def assert_relative(value, ref, rel, what):
+    value, ref = float(value), float(ref)
+    err = abs(value - ref)
+    assert err <= rel * abs(ref) and value == value, f"{what}: {value!r} vs {ref!r}: relative error {err / max(abs(ref), 1e-300):.3e} > {rel:.3e}"
+    return err / (rel * abs(ref)) if ref else 0.0
+
+
+# ---- RMSNorm
+def rstd_rel_bound(d):
+    """relative error of rstd = rsqrtf(ss / d + eps) against float64: d / 64 squares added per lane (the squares of bf16 values are exact),
+    six levels of the wave reduction, and 6 for the division, the eps addition and rsqrtf (2 ulp, halved by the square root's
+    derivative but counted whole)"""
+    return (d / 64 + 12) * U_F32
+
+
+def rmsnorm_fwd_reference(x, w, eps):
+    """(y, rstd) of the documented chain bf16(bf16(x . rstd) . w) with float64 statistics; eps as the fp32 value the kernel receives"""
+    x64 = f64(x)
+    rstd = (x64.pow(2).mean(-1) + float(torch.tensor(eps, dtype=torch.float32))).rsqrt()
+    return bf16_round(bf16_round(x64 * rstd[:, None]) * f64(w)), rstd
+
+
+def check_rmsnorm_fwd(y, rstd, x, w, eps, what, ref=None):
+    """y within 2 bf16 ulp everywhere and different on at most 0.1 %; rstd (when returned) relative within rstd_rel_bound(d).
+    -> dict(ulp, share, rstd = worst error / bound)"""
+    yref, r64 = rmsnorm_fwd_reference(x, w, eps) if ref is None else ref
+    ulp, share = assert_ulp(y, yref, 2, 1e-3, f"{what} y")
+    stat = dict(ulp=ulp, share=share, rstd=0.0)
+    if rstd is not None:
+        assert rstd.dtype == torch.float32
+        stat["rstd"] = assert_bounded(rstd, r64, rstd_rel_bound(x.shape[1]) * r64, f"{what} rstd", tile=(1, 1))
+    return stat
+
+
+def rmsnorm_bwd_dw_n_add(rows, d):
+    """Longest chain of fp32 roundings a term dy . xhat passes through on its way into dW[j] (csrc/norm.hip):
+         2                    xhat = x . rstd and the product dy . xhat
+       + rows per accumulator one wave (generic kernels: P . 8 waves stride the rows) or one row slot (d = 4096: P . 2 slots) adds its rows
+                              in turn into a register
+       + fold                 the 8 waves of a workgroup add into one LDS row in wave order: 7;  d = 4096: slot 1 onto slot 0: 1
+       + ceil(P / 16)         reduce_partials_kernel: row group g adds partial rows g, g + 16, ... in order
+       + 16                   the 16 group sums, added in order onto 0
+       + 1                    the old gradient under `accumulate`
+    with P = min(512, ceil(rows / 8)) workgroups = partial rows (mantis_rmsnorm_bwd_partials)."""
+    P = min(512, max(1, -(-rows // 8)))
+    per_acc, fold = (-(-rows // (2 * P)), 1) if d == 4096 else (-(-rows // (8 * P)), 7)
+    return 2 + per_acc + fold + -(-P // 16) + 16 + 1
+
+
+def rmsnorm_bwd_reference(dy, x, w, rstd, dres, g0, accumulate):
+    """float64 dx and dW from the DEVICE's rstd, with their bounds -> dict(dx, dx_bound, dw, dw_bound).
+
+    dx = rstd . (g - xhat . dot) + dres,  g = dy . w,  xhat = x . rstd,  dot = mean(g . xhat).  Roundings on the longest path, the one through
+    the dot: xhat 1, g 1, the product 1, d / 64 additions per lane, 6 reduction levels, the division 1 -- d / 64 + 6 for the chain plus
+    4 -- then xhat . dot, the subtraction, the factor rstd and the residual: 4 more, and 2 for the second-order terms: c = d / 64 + 6 + 10.
+    The d = 4096 kernel adds the four waves' sums of a row in order: + 4.  Each rounding is relative to a partial result that is no larger
+    than the sum of the |terms| it is made of, which is what multiplies c."""
+    d = x.shape[1]
+    r = f64(rstd)[:, None]
+    g, xhat = f64(dy) * f64(w), f64(x) * r
+    dot = (g * xhat).mean(-1, keepdim=True)
+    dx = r * (g - xhat * dot)
+    mag = (r * g).abs() + (r * xhat).abs() * (dot.abs() + (g * xhat).abs().mean(-1, keepdim=True))
+    if dres is not None:
+        dx = dx + f64(dres)
+        mag = mag + f64(dres).abs()
+    c = d / 64 + 6 + 10 + (4 if d == 4096 else 0)
+    res = dict(dx=dx, dx_bound=half_ulp_bf16(dx) + c * U_F32 * mag)
+    t = f64(dy) * xhat
+    dw, mag = t.sum(0), t.abs().sum(0)
+    if accumulate:
+        dw, mag = dw + f64(g0), mag + f64(g0).abs()
+    res.update(dw=dw, dw_bound=half_ulp_bf16(dw) + rmsnorm_bwd_dw_n_add(x.shape[0], d) * U_F32 * mag)
+    return res
+
+
+# ---- LayerNorm
+def layernorm_reference(x, w, b, eps):
+    """float64 y = (x - mean) . rstd . w + b and its bound
+         half ulp + c . 2^-24 . (|x - mean| . rstd . |w| + |b|) + rstd . |w| . (d / 64 + 6) . 2^-24 . mean |x|.
+    c = d / 64 + 16: rstd carries the chain of the squared deviations (d / 64 per lane + 6 levels; the deviation and its square 2, the
+    division, the eps addition and rsqrtf 4) and the value four pointwise roundings (x - mean, . rstd, . w, + b), 2 for second order.
+    The last term is the error of the mean itself (the same chain over the |x|), which enters y through x - mean without the factor
+    |x - mean|: it is what bounds a row whose deviations cancel (a constant row)."""
+    d = x.shape[1]
+    x64, w64, b64 = f64(x), f64(w), f64(b)
+    mean = x64.mean(-1, keepdim=True)
+    dev = x64 - mean
+    rstd = (dev.pow(2).mean(-1, keepdim=True) + float(torch.tensor(eps, dtype=torch.float32))).rsqrt()
+    ref = dev * rstd * w64 + b64
+    bound = (half_ulp_bf16(ref) + (d / 64 + 16) * U_F32 * (dev.abs() * rstd * w64.abs() + b64.abs())
+             + rstd * w64.abs() * (d / 64 + 6) * U_F32 * x64.abs().mean(-1, keepdim=True))
+    return ref, bound
+
+
+# ---- cross-entropy
+def ce_reference(logits, targets, V, grad_scale):
+    """float64 reference of ce.hip on logits [R, ld] (columns < V count) -> dict
+         valid [R], count = [valid rows, rows with a target >= V], lse [R] (0 on rows that are not valid), lse_bound [R], loss (mean over
+         the valid rows, NaN without one), dlogits [R, pad8(V)] (zero on rows that are not valid and on columns >= V), dl_bound.
+
+    lse_bound = (V / 1024 + 16) . 2^-24 . max(1, |lse|) + E,   E = (2 . range + 8 + 2 . ceil(V / 8192)) . 2^-24,
+    range = the row's largest minus its smallest finite logit.  The first term: a thread adds 8 . ceil(V / 8192) exponentials, then the
+    wave and block reductions and logf.  E is what __expf costs: it evaluates exp2(x . log2 e), and the fp32 rounding of that product is
+    an ABSOLUTE error |x| . 2^-24 of the exponent, i.e. a RELATIVE error |x| . 2^-24 of the exponential, |x| <= range (1 more for the
+    exp2 itself); the rescale factors __expf(m - nm) of a thread and __expf(m - gm) of the block reduction cost the same and their
+    arguments telescope to at most `range` again (2 . range in all), with one ulp each for the ceil(V / 8192) + 1 rescales and the
+    subtractions: 8 + 2 . ceil(V / 8192) covers them.  A relative error of the sum is an absolute error of its logarithm.
+
+    dl_bound = half ulp + c . 2^-24 . sc . (p . (1 + |x - lse|) + onehot),  sc = grad_scale / count,  c = lse_bound / 2^-24 + 4 per row:
+    p = __expf(x - lse) inherits the absolute error of lse and of the subtraction as a relative error (|x - lse| . 2^-24 twice: the
+    subtraction and the log2 e product), 1 for exp2, then `- 1` at the target, `. sc` and sc's own division: 4.  The bound is absolute at
+    the target, where p - 1 cancels: its terms p and onehot enter by their absolute values.  2^-126 on top: fp32 results below the
+    smallest normal number may be flushed to zero (p . sc reaches 1e-38 at the far end of an 80-wide ramp)."""
+    R_, Vp = logits.shape[0], (V + 7) // 8 * 8
+    x = f64(logits)[:, :V]
+    t = targets.cpu().long()
+    valid = (t >= 0) & (t < V)
+    cnt = int(valid.sum())
+    lse = torch.logsumexp(x, dim=-1)
+    fin = torch.isfinite(x)
+    rng = torch.where(fin, x, torch.full_like(x, -1e300)).amax(-1) - torch.where(fin, x, torch.full_like(x, 1e300)).amin(-1)
+    e_exp = (2 * rng + 8 + 2 * -(-V // 8192)) * U_F32
+    lse_bound = (V / 1024 + 16) * U_F32 * lse.abs().clamp_min(1.0) + e_exp
+    picked = x.gather(1, t.clamp(0, V - 1)[:, None])[:, 0]
+    loss = torch.where(valid, lse - picked, torch.zeros_like(lse)).sum() / cnt if cnt else torch.tensor(float("nan"), dtype=torch.float64)
+    sc = grad_scale / cnt if cnt else 0.0
+    p = torch.exp(x - lse[:, None])
+    onehot = torch.zeros_like(x)
+    onehot[torch.arange(R_)[valid], t[valid]] = 1.0
+    dl = torch.zeros(R_, Vp, dtype=torch.float64)
+    dl[:, :V] = (p - onehot) * sc * valid[:, None]
+    dist = torch.where(fin, (x - lse[:, None]).abs(), torch.zeros_like(x))
+    c = lse_bound / U_F32 + 4
+    bound = torch.zeros_like(dl)
+    bound[:, :V] = c[:, None] * U_F32 * sc * (p * (1 + dist) + onehot) * valid[:, None]
+    bound = bound + (half_ulp_bf16(dl) + 2.0 ** -126) * (dl != 0)
+    return dict(valid=valid, count=[cnt, int((t >= V).sum())], lse=torch.where(valid, lse, torch.zeros_like(lse)), lse_bound=lse_bound,
+                loss=loss, dlogits=dl, dl_bound=bound)
+
+
+# ---- RoPE
+def rope_table_reference(pos_rows, inv_freq):
+    """float64 cos / sin of the fp32 product float(pos) . inv_freq (one IEEE multiplication: the same on every machine); pos_rows [R, half]
+    holds the position each (row, frequency) reads (rope_table: pos[:, None]; sections: pos[sec[j], r])"""
+    f = (pos_rows.to(torch.float32) * inv_freq.to(torch.float32)[None]).to(torch.float64)
+    return f.cos(), f.sin()
+
+
+def rope_bwd_reference(x, cos, sin, nheads, hd):
+    """float64 transpose of the rotation on the first nheads . hd columns -> [R, nheads . hd]"""
+    Rr, half = x.shape[0], hd // 2
+    v = f64(x)[:, : nheads * hd].reshape(Rr, nheads, hd)
+    x1, x2 = v[..., :half], v[..., half:]
+    c, s = f64(cos)[:, None, :], f64(sin)[:, None, :]
+    return torch.cat([x1 * c + x2 * s, x2 * c - x1 * s], dim=-1).reshape(Rr, nheads * hd)
+
+
+# ---- reductions
+def colsum_n_add(M):
+    """act.hip: P = min(64, ceil(M / 128)) row blocks of rpb = ceil(M / P) rows; a thread adds every fourth row of its block
+    (ceil(rpb / 4)), the four row lanes are added (3), reduce_partials_kernel2 adds the P partial rows in order (P), then the old
+    gradient under `accumulate` (1)"""
+    P = min(64, max(1, -(-M // 128)))
+    return -(-(-(-M // P)) // 4) + 3 + P + 1
+
+
+def colsum_reference(x, g0, accumulate):
+    x64 = f64(x)
+    ref, mag = x64.sum(0), x64.abs().sum(0)
+    if accumulate:
+        ref, mag = ref + f64(g0), mag + f64(g0).abs()
+    return ref, half_ulp_bf16(ref) + colsum_n_add(x.shape[0]) * U_F32 * mag
+
+
+BLOCK_SUM_ADDS = 12      # common.h block_sum: six levels inside a wave, six more over the (at most 16) wave sums
+
+
+def sumsq_n_add(n):
+    """optim.hip mantis_sumsq: 8192 x 256 threads stride the n / 8 chunks, 8 additions per chunk (squares of bf16 values are exact in
+    fp32), block_sum; sumsq_finish_kernel: 1024 threads add 8 partials each, block_sum, and the accumulate"""
+    return 8 * max(1, -(-(n // 8) // (8192 * 256))) + BLOCK_SUM_ADDS + 8 + BLOCK_SUM_ADDS + 1
+
+
+def sumsq_range_n_add(n):
+    """sumsq_ranges_kernel: one 1024-thread workgroup per range"""
+    return 8 * max(1, -(-(n // 8) // 1024)) + BLOCK_SUM_ADDS
+
+
+def sum_f32_n_add(n):
+    """sum_f32_kernel: 1024 threads stride the array, block_sum, the accumulate"""
+    return max(1, -(-n // 1024)) + BLOCK_SUM_ADDS + 1
+
+
+def clip_scale_reference(sumsq, max_norm):
+    """float64 (scale, norm) from the fp32 sum the kernel read; held to 4 . 2^-24: sqrtf, the 1e-6 addition, the division, and one for
+    max_norm and 1e-6 being passed as fp32"""
+    s = float(sumsq)
+    norm = s ** 0.5
+    return min(1.0, float(torch.tensor(max_norm, dtype=torch.float32)) / (norm + float(torch.tensor(1e-6, dtype=torch.float32)))), norm

@@ -287,3 +287,313 @@ def test_single_key_window_backward_is_held_absolutely():
     bad[69, :hd] = 0
     with pytest.raises(AssertionError, match="dv"):
         case.check_backward(dq, dk, bad, "window 1, dv row-head zero")
+
+
+# ------------------------------------------------------------------------------------------------------------- row-wise kernels
+# (a) the fp32 oracle passes every criterion on the exact inputs of tests/test_rowwise_local_error_gpu.py (tests/rowwise_cases.py holds
+# both); (b) every seeded fault, applied to a CPU emulation of the kernel's arithmetic, is rejected.
+from oracle import ops_ref as OR          # noqa: E402
+from tests import rowwise_cases as C      # noqa: E402
+
+CPU = "cpu"
+
+
+@pytest.mark.parametrize("d,rows,w_off", [c[1:] for c in C.RMS_FWD_CASES], ids=[c[0] for c in C.RMS_FWD_CASES])
+def test_oracle_passes_rmsnorm_fwd(d, rows, w_off):
+    print(C.run_rmsnorm_fwd(OR, CPU, d, rows, w_off))
+
+
+@pytest.mark.parametrize("d,sub", [c[1:] for c in C.RMS_BWD_CASES], ids=[c[0] for c in C.RMS_BWD_CASES])
+def test_oracle_passes_rmsnorm_bwd(d, sub):
+    print(C.run_rmsnorm_bwd(OR, CPU, d, sub))
+
+
+@pytest.mark.parametrize("rows,d", C.RMS_BWD_WITNESS)
+def test_oracle_passes_rmsnorm_bwd_witness(rows, d):
+    C.run_rmsnorm_bwd_witness(OR, CPU, rows, d)
+
+
+@pytest.mark.parametrize("d,rows", C.LN_CASES, ids=[f"d{c[0]}" for c in C.LN_CASES])
+def test_oracle_passes_layernorm(d, rows):
+    print(C.run_layernorm(OR, CPU, d, rows))
+
+
+@pytest.mark.parametrize("V", C.CE_V)
+def test_oracle_passes_ce(V):
+    for kind in C.CE_KINDS:
+        print(kind, C.run_ce(OR, CPU, V, kind))
+
+
+def test_oracle_passes_ce_edge_rows():
+    C.run_ce_all_ignored(OR, CPU)
+    for V in C.CE_NEG_INF_V:
+        C.run_ce_neg_inf(OR, CPU, V)
+
+
+@pytest.mark.parametrize("hd,nheads,R_", C.ROPE_CASES)
+def test_oracle_passes_rope_apply(hd, nheads, R_):
+    stat = C.run_rope_apply(OR, CPU, hd, nheads, R_)
+    assert stat["bwd_share"] == 0.0, stat             # the cap of 0.1 % is held by the reference alone
+
+
+@pytest.mark.parametrize("half", C.ROPE_TABLE_HALF)
+def test_oracle_passes_rope_tables(half):
+    for stat in (C.run_rope_table(OR, CPU, half), C.run_rope_table_sections(OR, CPU, 3, half), C.run_rope_table_sections(OR, CPU, 2, half)):
+        assert stat["share"] == 0.0, stat
+
+
+def test_oracle_passes_reductions():
+    for M in C.COLSUM_M:
+        C.run_colsum(OR, CPU, M)
+    for n in C.SUMSQ_N:
+        C.run_sumsq(OR, CPU, n)
+    C.run_sumsq_ranges(OR, CPU)
+    for n in C.SUM_F32_N:
+        C.run_sum_f32(OR, CPU, n)
+    C.run_clip_scale(OR, CPU)
+
+
+def _bf(t):
+    return t.to(BF).float()
+
+
+# ---- RMSNorm forward
+def _emu_rmsnorm_fwd(x, w, eps, fault=None):
+    xf, wf, d = x.float(), w.float(), x.shape[1]
+    ms = xf.pow(2).mean(-1)
+    if fault == "row_denominator":                      # one row normalised with d + 8 in the denominator
+        ms[x.shape[0] // 2] = xf[x.shape[0] // 2].pow(2).sum() / (d + 8)
+    rstd = torch.rsqrt(ms + eps)
+    if fault == "single_rounding":
+        return (xf * rstd[:, None] * wf).to(BF), rstd
+    n = _bf(xf * rstd[:, None])
+    y = (n * wf).to(BF)
+    if fault == "neighbour_weights":                    # one 8-chunk scaled by its neighbour's weights
+        c = d // 16 * 8
+        y[:, c:c + 8] = (n[:, c:c + 8] * wf[c + 8:c + 16]).to(BF)
+    return y, rstd
+
+
+@pytest.mark.parametrize("rows,d", [(323, 768), (37, 3584), (16, 8192)])
+def test_rmsnorm_fwd_emulation_differs_nowhere(rows, d):
+    x, w = rnd(rows, d, seed=1), C._weight(d, 2)
+    stat = LE.check_rmsnorm_fwd(*_emu_rmsnorm_fwd(x, w, 1e-5), x, w, 1e-5, f"emulation {rows}x{d}")
+    assert stat["share"] == 0.0 and stat["ulp"] == 0, stat
+
+
+@pytest.mark.parametrize("fault", ["single_rounding", "row_denominator", "neighbour_weights"])
+def test_rmsnorm_fwd_seeded_fault_is_rejected(fault):
+    x, w = rnd(323, 768, seed=1), C._weight(768, 2)
+    y, rstd = _emu_rmsnorm_fwd(x, w, 1e-5, fault)
+    with pytest.raises(AssertionError, match="rmsnorm y"):
+        LE.check_rmsnorm_fwd(y, None, x, w, 1e-5, "rmsnorm")            # the output alone gives it away
+    if fault == "row_denominator":
+        with pytest.raises(AssertionError, match="rstd"):
+            LE.check_rmsnorm_fwd(_emu_rmsnorm_fwd(x, w, 1e-5)[0], rstd, x, w, 1e-5, "rmsnorm")
+    if fault == "single_rounding":                                       # the reason: the whole-tensor bar lets it through
+        close(y, OR.rmsnorm_fwd(x, w, 1e-5)[0], 4e-3, "old bar, single rounding")
+
+
+# ---- RMSNorm backward
+def _emu_rmsnorm_bwd(dy, x, w, rstd, dres, g0, fault=None):
+    rows, d = x.shape
+    xf, g = x.float(), dy.float() * w.float()
+    xhat = xf * rstd[:, None]
+    prod = g * xhat
+    dot = (prod[:, :-8] if fault == "dot_last_chunk" else prod).sum(-1, keepdim=True) / d
+    add = dres.float().clone()
+    if fault == "dres_last_row":
+        add[-1] = 0
+    dx = (rstd[:, None] * (g - xhat * dot) + add).to(BF)
+    t = dy.float() * xhat
+    if fault == "dw_row":
+        t[rows // 2] = 0
+    if fault == "dw_partial_row":                       # one workgroup's partial row: 8 rows
+        t[8:16] = 0
+    gw = t.sum(0) + g0.float()
+    if fault == "dw_swap":
+        j = d // 2
+        gw[[j, j + 8]] = gw[[j + 8, j]]
+    return dx, gw.to(BF)
+
+
+@pytest.fixture(scope="module")
+def rms_bwd_case():
+    rows, d = 323, 768
+    x, w, dy, dres, g0 = rnd(rows, d, seed=1), C._weight(d, 2), rnd(rows, d, seed=3), rnd(rows, d, seed=4), rnd(d, seed=5)
+    rstd = LE.rmsnorm_fwd_reference(x, w, 1e-5)[1].float()
+    return (dy, x, w, rstd, dres, g0), LE.rmsnorm_bwd_reference(dy, x, w, rstd, dres, g0, True)
+
+
+@pytest.mark.parametrize("fault", [None, "dot_last_chunk", "dres_last_row", "dw_row", "dw_partial_row", "dw_swap"])
+def test_rmsnorm_bwd_seeded_fault_is_rejected(rms_bwd_case, fault):
+    args, ref = rms_bwd_case
+    dx, gw = _emu_rmsnorm_bwd(*args, fault=fault)
+    hits = []
+    for name, out in (("dx", dx), ("dw", gw)):
+        try:
+            LE.assert_bounded(out, ref[name], ref[name + "_bound"], name)
+        except AssertionError:
+            hits.append(name)
+    assert hits == ([] if fault is None else ["dw"] if fault.startswith("dw") else ["dx"]), hits
+
+
+@pytest.mark.parametrize("rows,d", C.RMS_BWD_WITNESS)
+def test_rmsnorm_bwd_witness_sees_a_row_counted_twice(rows, d):
+    class Twice:
+        @staticmethod
+        def rmsnorm_bwd(dy, x, w, rstd, dres, g, acc, amax_parts=None):
+            dy = dy.clone()
+            dy[rows - 1] *= 2                           # the last row's contribution added twice
+            return OR.rmsnorm_bwd(dy, x, w, rstd, dres, g, acc)
+    with pytest.raises(AssertionError, match="witness"):
+        C.run_rmsnorm_bwd_witness(Twice, CPU, rows, d)
+
+
+# ---- LayerNorm
+def _emu_layernorm(x, w, b, eps, fault=None):
+    xf, wf, bf_ = x.float(), w.float(), b.float().clone()
+    mean = xf.mean(-1, keepdim=True)
+    if fault == "one_pass_variance":                    # fp32 E[x^2] - mean^2: cancels catastrophically at mean 30, std 1
+        var = (xf * xf).mean(-1, keepdim=True) - mean * mean
+    else:
+        var = (xf - mean).pow(2).mean(-1, keepdim=True)
+    if fault == "bias_shift":                           # the bias of one chunk read 8 elements further
+        c = x.shape[1] // 16 * 8
+        bf_[c:c + 8] = b.float()[c + 8:c + 16]
+    return ((xf - mean) * torch.rsqrt(var + eps) * wf + bf_).to(BF)
+
+
+@pytest.mark.parametrize("rows,d", [(5, 768), (37, 768), (323, 1152)])      # the first is a GPU case as it stands
+@pytest.mark.parametrize("fault", [None, "one_pass_variance", "bias_shift"])
+def test_layernorm_seeded_fault_is_rejected(fault, rows, d):
+    """the one-pass variance errs by about 2^-24 . mean^2 / var relative, the bound's mean term allows (d / 64 + 6) . 2^-24 . mean absolute:
+    at mean 30 the fault stands out by a factor 30 / (d / 64 + 6) -- clear at d = 768, 10 elements of 3840 over the bound, thin at 5 x 1152,
+    where it takes more rows to meet an element next to a rounding tie"""
+    x, w, b = C.ln_inputs(rows, d)
+    ref, bound = LE.layernorm_reference(x, w, b, 1e-6)
+    y = _emu_layernorm(x, w, b, 1e-6, fault)
+    if fault is None:
+        LE.assert_bounded(y, ref, bound, "layernorm emulation")
+        return
+    with pytest.raises(AssertionError, match="over the bound"):
+        LE.assert_bounded(y, ref, bound, fault)
+
+
+# ---- cross-entropy
+def _emu_ce(x0, tgt, V, fault=None):
+    """ce.hip in fp32 with its thread layout: thread t of 1024 owns the 8-chunks t, t + 1024, ... and keeps an online (max, sum)"""
+    R_, Vp = x0.shape[0], C.pad8(V)
+    xf = x0.float()[:, :Vp]
+    seen = Vp if fault == "pad_in_lse" else V
+    trips = -(-(Vp // 8) // 1024)
+    buf = torch.full((R_, trips * 8192), float("-inf"))
+    buf[:, :seen] = xf[:, :seen]
+    buf = buf.reshape(R_, trips, 1024, 8)
+    m, s = torch.full((R_, 1024), float("-inf")), torch.zeros(R_, 1024)
+    for i in range(trips):
+        c = buf[:, i]
+        nm = torch.maximum(m, c.amax(-1))
+        acc = torch.exp(c - nm[..., None]).nan_to_num(0.0).sum(-1)
+        s = s * (1.0 if fault == "no_rescale" else torch.exp(m - nm).nan_to_num(0.0)) + acc
+        m = nm
+    gm = m.amax(-1, keepdim=True)
+    lse = gm[:, 0] + torch.log((s * torch.exp(m - gm).nan_to_num(0.0)).sum(-1))
+    t = tgt.long()
+    valid = (t >= 0) & (t < V)
+    sc = C.GSCALE / (R_ if fault == "scale_by_rows" else int(valid.sum()))
+    g = torch.zeros(R_, Vp)
+    g[:, :V] = torch.exp(xf[:, :V] - lse[:, None])
+    hot = torch.where(t + 1 < V, t + 1, t - 1) if fault == "target_off_by_one" else t
+    g[torch.arange(R_)[valid], hot[valid]] -= 1.0
+    g = g * sc * valid[:, None]
+    return g.to(BF), torch.where(valid, lse, torch.zeros_like(lse))
+
+
+@pytest.mark.parametrize("V,kind", [(300, "normal3"), (16389, "ramp_up"), (32002, "ramp_down")])
+@pytest.mark.parametrize("fault", [None, "pad_in_lse", "no_rescale", "scale_by_rows", "target_off_by_one"])
+def test_ce_seeded_fault_is_rejected(fault, V, kind):
+    tgt = C.ce_targets(V)
+    x0 = C.ce_logits(V, kind, tgt, C.pad8(V) + 24)
+    ref = LE.ce_reference(x0, tgt, V, C.GSCALE)
+    dl, lse = _emu_ce(x0, tgt, V, fault)
+    hits = []
+    for name, check in (("lse", lambda: LE.assert_bounded(lse, ref["lse"], ref["lse_bound"] * ref["valid"], "lse", tile=(1, 1))),
+                        ("dl", lambda: LE.assert_bounded(dl, ref["dlogits"], ref["dl_bound"], "dlogits"))):
+        try:
+            check()
+        except AssertionError:
+            hits.append(name)
+    if fault is None:
+        assert hits == []
+    elif fault == "no_rescale" and (V <= 8192 or kind == "ramp_down"):
+        assert hits == []                               # one chunk per thread, or a maximum that never rises: the rescale is idle -- which is
+    elif fault == "pad_in_lse" and V % 8 == 0:          # why the GPU cases carry V > 8192 with a rising ramp, and V % 8 != 0
+        assert hits == []
+    elif fault in ("pad_in_lse", "no_rescale"):
+        assert hits == ["lse", "dl"]
+    else:
+        assert hits == ["dl"]
+
+
+# ---- RoPE
+def _emu_rope(x, cos, sin, nheads, hd, backward=False, fault=None):
+    if fault == "table_row_shift":                      # row r rotated with table row r + 1
+        cos, sin = cos.roll(-1, 0), sin.roll(-1, 0)
+    out = OR.rope_apply_(x.clone(), cos, sin, nheads, hd, backward=backward)
+    half = hd // 2
+    if fault == "sine_sign_one_head":
+        h = nheads - 1
+        out[:, h * hd:(h + 1) * hd] = OR.rope_apply_(x[:, h * hd:(h + 1) * hd].clone(), cos, -sin, 1, hd, backward=backward)
+    if fault == "single_rounding":
+        v = x.float().reshape(x.shape[0], nheads, hd)
+        x1, x2, c, s = v[..., :half], v[..., half:], cos.float()[:, None], sin.float()[:, None]
+        out = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1).reshape(x.shape[0], -1).to(BF)
+    return out
+
+
+@pytest.mark.parametrize("hd", [16, 80, 128])
+@pytest.mark.parametrize("fault", ["sine_sign_one_head", "table_row_shift", "single_rounding"])
+def test_rope_seeded_fault_is_rejected(fault, hd):
+    nheads, R_ = 6, 77
+    cos, sin = OR.rope_table(C.rope_positions(R_, hd), C.inv_freq(hd // 2))
+    x = rnd(R_, nheads * hd, seed=hd)
+    with pytest.raises(AssertionError, match="not bit-equal"):
+        LE.assert_bit_equal(_emu_rope(x, cos, sin, nheads, hd, fault=fault), OR.rope_apply_(x.clone(), cos, sin, nheads, hd), fault)
+    if fault != "single_rounding":                      # the backward has one rounding by design
+        with pytest.raises(AssertionError):
+            LE.assert_ulp(_emu_rope(x, cos, sin, nheads, hd, True, fault), LE.rope_bwd_reference(x, cos, sin, nheads, hd), 1, 1e-3, fault)
+    cref, _ = LE.rope_table_reference(C.rope_positions(R_, hd)[:, None].expand(R_, hd // 2), C.inv_freq(hd // 2))
+    with pytest.raises(AssertionError):                 # and the table criterion sees a table shifted by one row
+        LE.assert_ulp(cos.roll(-1, 0), cref, 1, 1e-3, "shifted table")
+
+
+# ---- colsum
+@pytest.mark.parametrize("fault", [None, "last_row_block", "accumulate_ignored"])
+@pytest.mark.parametrize("M,N", [(129, 65), (777, 300), (8193, 64)])
+def test_colsum_seeded_fault_is_rejected(M, N, fault):
+    x, g0 = rnd(M, N, seed=M + N), rnd(N, seed=N)
+    ref, bound = LE.colsum_reference(x, g0, True)
+    P = min(64, -(-M // 128))
+    keep = M - (M - (P - 1) * -(-M // P)) if fault == "last_row_block" else M
+    out = (x.float()[:keep].sum(0) + (0 if fault == "accumulate_ignored" else g0.float())).to(BF)
+    if fault is None:
+        LE.assert_bounded(out, ref, bound, "colsum emulation", tile=(1, 64))
+        return
+    with pytest.raises(AssertionError, match="over the bound"):
+        LE.assert_bounded(out, ref, bound, fault, tile=(1, 64))
+
+
+def test_exact_witnesses_see_a_row_counted_twice():
+    class Twice:
+        @staticmethod
+        def colsum(x, grad, accumulate):
+            OR.colsum(torch.cat([x, x[-1:]]) if bool(((x == 0) | (x == 1)).all()) else x, grad, accumulate)      # the witness input only
+
+        @staticmethod
+        def grad_sumsq(x, out, accumulate=False, ws=None):
+            OR.grad_sumsq(torch.cat([x, x[-8:]]) if bool((x.abs() == 1).all()) else x, out, accumulate)
+    with pytest.raises(AssertionError, match="witness"):
+        C.run_colsum(Twice, CPU, 129)
+    with pytest.raises(AssertionError, match="witness"):
+        C.run_sumsq(Twice, CPU, 8000)
