@@ -377,6 +377,15 @@ int mantis_attn_decode_splits(int B, int Hkv, int S_max);                       
 int mantis_attn_decode_workspace_bytes(int B, int H, int Hkv, int hd, int S_max);   /* returns bytes */
 /* out[b] (int64) = index of the maximum of logits[b, 0 .. V) (bf16, row stride ld); ties resolve to the LOWEST index; NaN-free input assumed. */
 int mantis_argmax_rows(const void* logits, int64_t ld, int B, int V, int64_t* out, void* stream);
+/* One step of greedy search for every row b, one workgroup per row, mantis_argmax_rows' reduction (ties to the LOWEST index, columns [V, ld)
+ * never read), finished-ness kept on the device:
+ *   t = argmax(logits[b, 0 .. V));  if n_eos > 0 and unfinished[b] == 0: t = pad_id
+ *   out[b * ldo + step] = t;  next_tokens[b] = t
+ *   if n_eos > 0 and unfinished[b] != 0 and t in eos_ids[0 .. n_eos): unfinished[b] = 0, finish_step[b] = step
+ * eos_ids int64 [n_eos] on the device; unfinished, finish_step int32 [B] (the caller initialises them to 1 and -1); with n_eos == 0 the three
+ * may be NULL and are not touched.  0 <= step < ldo.  Plain stores by one thread per row: no atomics, deterministic. */
+int mantis_greedy_select(const void* logits, int64_t ld, int B, int V, const int64_t* eos_ids, int n_eos, int64_t pad_id, int32_t* unfinished,
+                         int32_t* finish_step, int64_t* out, int64_t ldo, int step, int64_t* next_tokens, void* stream);
 
 /* Idefics3 connector's pixel shuffle (reference: mantis/models/idefics3/modeling_idefics3.py:651-660), a row permutation over the
  * square H x H patch grid of each of the I images (x: [I*H*H, C] rows of stride ldx; out: [I*(H/s)^2, s*s*C] rows of stride ldo):

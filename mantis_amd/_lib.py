@@ -87,6 +87,7 @@ SIGNATURES = {
     "mantis_attn_decode_splits": [I, I, I],
     "mantis_attn_decode_workspace_bytes": [I, I, I, I, I],
     "mantis_argmax_rows": [P, L, I, I, P, P],
+    "mantis_greedy_select": [P, L, I, I, P, I, L, P, P, P, L, I, P, P],
     "mantis_pixel_shuffle": [P, L, P, L, I, I, I, I, P],
     "mantis_version": [],
 }

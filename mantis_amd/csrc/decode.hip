@@ -15,6 +15,8 @@
 //                   16 bytes per lane straight to VGPRs; online softmax per lane, fp32 partial (m, l, o) per split to a caller-owned
 //                   workspace, a combine kernel sums the splits in split order.
 //   argmax_rows   : first V columns of bf16 logits -> int64 index, ties to the lowest index.
+//   greedy_select : the same argmax + one step of greedy search's bookkeeping (pad fill, column write, EOS test) with the finished flags
+//                   kept on the device.
 // All four are deterministic (fixed summation orders).
 #include "common.h"
 
@@ -320,6 +322,58 @@ __global__ __launch_bounds__(1024) void argmax_rows_kernel(const bf16_t* __restr
     if (tid == 0) out[blockIdx.x] = (long)s_i[0];
 }
 
+// ------------------------------------------------------------------------------------------------------------------ greedy select
+// argmax_rows_kernel's reduction (same strided scan, same tree, same tie rule) followed by one step of greedy search's bookkeeping for the
+// row: pad fill of a finished row, the column write, the EOS test.  Row b's flags are read and written by thread 0 of workgroup b only.
+__global__ __launch_bounds__(1024) void greedy_select_kernel(const bf16_t* __restrict__ x, long ld, int V, const long* __restrict__ eos_ids,
+                                                             int n_eos, long pad_id, int* __restrict__ unfinished, int* __restrict__ finish_step,
+                                                             long* __restrict__ out, long ldo, int step, long* __restrict__ next_tokens) {
+    __shared__ float s_v[1024];
+    __shared__ int s_i[1024];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x;
+    const bf16_t* row = x + (long)b * ld;
+    float best = 0.f;
+    int bi = -1;
+    for (int i = tid; i < V; i += 1024) {        // ascending i: a strict comparison keeps the lowest index of equal values
+        const float v = bf2f(row[i]);
+        if (bi < 0 || v > best) {
+            best = v;
+            bi = i;
+        }
+    }
+    s_v[tid] = best;
+    s_i[tid] = bi;
+    __syncthreads();
+    for (int off = 512; off > 0; off >>= 1) {
+        if (tid < off) {
+            const float v2 = s_v[tid + off];
+            const int i2 = s_i[tid + off];
+            const float v1 = s_v[tid];
+            const int i1 = s_i[tid];
+            if (i2 >= 0 && (i1 < 0 || v2 > v1 || (v2 == v1 && i2 < i1))) {
+                s_v[tid] = v2;
+                s_i[tid] = i2;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    long t = (long)s_i[0];
+    if (n_eos > 0) {
+        const bool live = unfinished[b] != 0;
+        if (!live) t = pad_id;
+        bool hit = false;
+        for (int e = 0; e < n_eos; ++e) hit = hit || (eos_ids[e] == t);
+        if (live && hit) {
+            unfinished[b] = 0;
+            finish_step[b] = step;
+        }
+    }
+    out[(long)b * ldo + step] = t;
+    next_tokens[b] = t;
+}
+
 extern "C" {
 
 int mantis_linear_skinny_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int M, int N, int K,
@@ -389,6 +443,16 @@ int mantis_argmax_rows(const void* logits, int64_t ld, int B, int V, int64_t* ou
     if (B < 0 || V < 1) return MANTIS_EINVAL;
     if (B == 0) return MANTIS_OK;
     MANTIS_LAUNCH(argmax_rows_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, (const bf16_t*)logits, (long)ld, V, (long*)out);
+    return mantis_check_launch();
+}
+
+int mantis_greedy_select(const void* logits, int64_t ld, int B, int V, const int64_t* eos_ids, int n_eos, int64_t pad_id, int32_t* unfinished,
+                         int32_t* finish_step, int64_t* out, int64_t ldo, int step, int64_t* next_tokens, void* stream) {
+    if (B < 0 || V < 1 || n_eos < 0 || step < 0 || ldo < 1 || step >= ldo || ld < V || !logits || !out || !next_tokens) return MANTIS_EINVAL;
+    if (n_eos > 0 && (!eos_ids || !unfinished || !finish_step)) return MANTIS_EINVAL;
+    if (B == 0) return MANTIS_OK;
+    MANTIS_LAUNCH(greedy_select_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, (const bf16_t*)logits, (long)ld, V, (const long*)eos_ids,
+                  n_eos, (long)pad_id, (int*)unfinished, (int*)finish_step, (long*)out, (long)ldo, step, (long*)next_tokens);
     return mantis_check_launch();
 }
 

@@ -57,6 +57,19 @@ class LlavaEngine:
         self.weights_unchanged = False       # set by MantisHipTrainer on the 2nd.. micro-batch of an accumulation window
         self._prefetched = BB.PrefetchSlots()     # towers computed ahead by prefetch_vision: (pixel_values object, feats, N, done event)
 
+    @property
+    def K(self):
+        """the operator backend (generation.py asks the engine, not a module): the module-level name the tests monkeypatch"""
+        return K
+
+    prefill_positions_follow_mask = False     # a padded TEXT-ONLY batch prefills with arange positions (the reference's forward): refused
+
+    def prefill_inputs(self, attention_mask, pixel_attention_mask=None):
+        """the family's extra keyword arguments of `step` for generation's prefill: none on this path"""
+        if pixel_attention_mask is not None:
+            raise NotImplementedError("generate(): argument `pixel_attention_mask` is not supported on the LLaVA path")
+        return {}
+
     def _verify_device_status(self, plan, count):
         st = plan.status.cpu().tolist()
         if st[0] == 2:

@@ -737,6 +737,33 @@ def argmax_rows(logits, V):
     return out
 
 
+def greedy_select(logits, V, eos_ids, pad_id, unfinished, finish_step, out, step, next_tokens):
+    """One step of greedy search on the device (csrc/decode.hip: greedy_select_kernel): next_tokens[b] = out[b, step] = argmax of the first V
+    columns of row b (ties to the lowest index), or pad_id where unfinished[b] == 0; a live row whose token is one of eos_ids gets
+    unfinished[b] = 0 and finish_step[b] = step.  eos_ids int64 [n] or None (then unfinished / finish_step are not touched and may be None);
+    unfinished, finish_step int32 [B]; out int64 [B, >= step + 1] with unit column stride; next_tokens int64 [B].  Returns next_tokens."""
+    _chk2d(logits, "logits")
+    B = logits.shape[0]
+    n_eos = 0 if eos_ids is None else eos_ids.numel()
+    if not 1 <= V <= logits.shape[1]:
+        raise ValueError(f"greedy_select: V={V} outside the logits' {logits.shape[1]} columns")
+    if out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != B or out.stride(1) != 1 or not 0 <= step < out.shape[1]:
+        raise ValueError(f"greedy_select: out {out.dtype} {tuple(out.shape)} stride {out.stride()} for B={B}, step={step}")
+    if next_tokens.dtype != torch.int64 or next_tokens.numel() != B or not next_tokens.is_contiguous():
+        raise ValueError("greedy_select: next_tokens must be contiguous int64 [B]")
+    if n_eos:
+        if eos_ids.dtype != torch.int64 or not eos_ids.is_contiguous() or eos_ids.device != logits.device:
+            raise ValueError("greedy_select: eos_ids must be contiguous int64 on the logits' device")
+        for t, n in ((unfinished, "unfinished"), (finish_step, "finish_step")):
+            if t is None or t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous():
+                raise ValueError(f"greedy_select: {n} must be contiguous int32 [B]")
+    rc = _L.mantis_greedy_select(_p(logits), logits.stride(0), B, V, _p(eos_ids) if n_eos else None, n_eos, int(pad_id) if n_eos else 0,
+                                 _p(unfinished) if n_eos else None, _p(finish_step) if n_eos else None, _p(out), out.stride(0), step,
+                                 _p(next_tokens), _stream())
+    _lib.check(rc, "greedy_select")
+    return next_tokens
+
+
 # ----------------------------------------------------------------------------------------------------------- packing / loss
 class PackPlan:
     __slots__ = ("B", "T", "L", "N", "I", "src", "attention_mask", "labels", "position_ids", "kmask", "text_pos", "img_slot",

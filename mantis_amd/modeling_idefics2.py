@@ -317,6 +317,20 @@ class Idefics2Engine:
         self.weights_unchanged = False       # set by MantisHipTrainer on the 2nd.. micro-batch of an accumulation window
         self._prefetched = BB.PrefetchSlots()     # (pixel_values object, feats, N, I, km_all, done event) of prefetch_vision
 
+    @property
+    def K(self):
+        """the operator backend (generation.py asks the engine, not a module): the module-level name the tests monkeypatch"""
+        return K
+
+    prefill_positions_follow_mask = True      # generation's prefill positions skip the padding: a padded text-only batch is fine
+
+    def prefill_inputs(self, attention_mask, pixel_attention_mask=None):
+        """the family's extra keyword arguments of `step` for generation's prefill: the pixel mask and the reference's generation
+        positions, `attention_mask.cumsum(-1) - 1` with masked positions at 1 (idefics3 modeling_idefics3.py:1243-1249)"""
+        am = attention_mask.to(torch.int64)
+        pos = am.cumsum(-1) - 1
+        return dict(pixel_attention_mask=pixel_attention_mask, position_ids=pos.masked_fill(am == 0, 1))
+
     def step_from_batch(self, inputs, launch=None, **kw):
         """launch: the caller's `launch.LaunchContext`, in force for exactly this call (see engine.LlavaEngine.step_from_batch)"""
         if kw.get("segment_ids") is None and inputs.get("segment_ids") is not None:
@@ -512,8 +526,17 @@ class Idefics2Engine:
 
     # ------------------------------------------------------------------ full step
     def step(self, input_ids, attention_mask, labels, pixel_values, pixel_attention_mask=None, grad_scale=1.0, loss_scale=1.0,
-             compute_grads=True, overwrite_grads=True, need_logits=False, record=None, on_bucket_ready=None, segment_ids=None):
+             compute_grads=True, overwrite_grads=True, need_logits=False, record=None, on_bucket_ready=None, segment_ids=None,
+             kv_sink=None, position_ids=None):
+        """kv_sink (generation.prefill, with compute_grads=False and no labels): receives every decoder layer's fused q|k|v
+        (decoder.decoder_forward); the step then stops before the head and returns dict(hidden=[B*T, d] before the final norm, plan=...,
+        L=T), as engine.LlavaEngine.step does.
+        position_ids (int64 [B, T]): replaces the default arange(T).  Generation prefills with the reference's
+        `attention_mask.cumsum(-1) - 1` (masked positions at 1; idefics3 modeling_idefics3.py:1243-1249) so that a left-padded prompt's
+        keys sit at the positions its new tokens count from.  An engine-level argument: `forward(position_ids=...)` keeps refusing."""
         m, cfg, tc = self.m, self.cfg, self.cfg.text_config
+        if kv_sink is not None and (compute_grads or labels is not None):
+            raise ValueError("kv_sink is the prefill of generation: compute_grads=False, no labels")
         dev = m.device
         ids_cpu = BB.to_host(input_ids)
         B, T = ids_cpu.shape
@@ -562,7 +585,14 @@ class Idefics2Engine:
         # inputs_merger (:1545-1565) = the packing plan with ONE slot per <image> token: slot r takes image-hidden row r in row-major
         # order; labels equal to image_token_id are the ignored ones (:1898); positions are Mistral's default arange
         plan = K.pack_plan(ids_d, attn_d, lab_d, 1, n_rows, IMG if img is not None else -(2 ** 62), -1, self.ignore_index, T)
-        plan.position_ids = torch.arange(T, device=dev, dtype=torch.int64)[None].expand(B, T).contiguous()
+        if position_ids is None:
+            plan.position_ids = torch.arange(T, device=dev, dtype=torch.int64)[None].expand(B, T).contiguous()
+        else:
+            if segment_ids is not None:
+                raise ValueError("position_ids and segment_ids both set: packed rows derive their own positions")
+            if tuple(position_ids.shape) != (B, T):
+                raise ValueError(f"position_ids {tuple(position_ids.shape)} for input_ids [{B}, {T}]")
+            plan.position_ids = position_ids.to(dev, non_blocking=True).to(torch.int64).contiguous()
         kstart = qend = None
         if segment_ids is not None:
             # long-sequence packing (BASELINE configs[3]; /root/reference/mantis/train/data.py:1546-1671): several samples in one row,
@@ -578,6 +608,9 @@ class Idefics2Engine:
         if record is not None and img is not None:
             record["merged_embeds"] = x.view(B, T, -1)
         kmask = None if D.no_padding(am_cpu, 0, T) else plan.kmask      # no pad position in the batch: no key mask (host-side decision)
+        if kv_sink is not None:
+            x, _ = D8.forward(K, self, m.lm, tc, x, B, T, plan.position_ids, kmask, kstart, False, record, kv_sink=kv_sink)
+            return dict(hidden=x, plan=plan, L=T)
         x, dctx = D8.forward(K, self, m.lm, tc, x, B, T, plan.position_ids, kmask, kstart, compute_grads, record,
                              checkpoint=m.is_gradient_checkpointing)
         if seqcls:

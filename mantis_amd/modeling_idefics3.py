@@ -14,7 +14,11 @@ torch's default ignore index -100.  Unlike on the Idefics2 path, a label equal t
 (train_idefics3.py:161) steers the collator, it does not reach this loss.  Reproduced here as it is; a collator that wants such positions
 ignored must write -100.
 
-Out of scope: generation / KV cache, the image processor and its tile splitting, LoRA / QLoRA, and the fp8 decoder variant
+GENERATION: `generate` is greedy search with a KV cache (generation.py), as mantis/mllm_tools/idefics3_eval.py:64 calls the reference
+class; the prefill is this engine's evaluation forward at the reference's generation positions (`attention_mask.cumsum(-1) - 1`), the
+decode steps are the LLaVA path's Llama-3 decode kernels.  `forward` itself keeps refusing the cache arguments.
+
+Out of scope: sampling / beam search, the image processor and its tile splitting, LoRA / QLoRA, and the fp8 decoder variant
 (`set_precision("fp8")` refuses by name)."""
 import torch
 
@@ -33,7 +37,7 @@ class Idefics3CausalLMOutputWithPast(Idefics2CausalLMOutputWithPast):
 class Idefics3ForConditionalGeneration(Idefics2ForConditionalGeneration):
     """`model(**batch).loss.backward()` (arena.FusedStep), `MantisHipTrainer` / `as_hf_trainer()`, `grad_buckets()`,
     `gradient_checkpointing_enable()`, `FusedAdamW` and the low-priority tower prefetch work as on the Idefics2 path: the forward
-    contract, the refusals (KV cache, inputs_embeds, image_hidden_states, output_attentions / output_hidden_states, explicit
+    contract, the refusals (KV cache arguments of `forward`, inputs_embeds, image_hidden_states, output_attentions / output_hidden_states, explicit
     position_ids -> NotImplementedError) and the gradient buckets ('front' = connector projection + token embedding) are inherited."""
     config_class = Idefics3Config
     output_class = Idefics3CausalLMOutputWithPast
@@ -51,6 +55,21 @@ class Idefics3ForConditionalGeneration(Idefics2ForConditionalGeneration):
 
     def _build_connector_grad_views(self, gv):
         self.grads_conn = dict(proj=gv(PROJ))
+
+    def generate(self, input_ids=None, pixel_values=None, pixel_attention_mask=None, attention_mask=None, max_new_tokens=None,
+                 max_length=None, eos_token_id=None, pad_token_id=None, do_sample=False, num_beams=1, streamer=None, **rest):
+        """Greedy search exactly as HF's `generate` returns it for the reference class (mantis/mllm_tools/idefics3_eval.py:64:
+        `model.generate(**inputs, max_new_tokens=512, num_beams=1)` with the processor's input_ids, attention_mask, pixel_values
+        [B, images, 3, H, W] and pixel_attention_mask): LongTensor [B, T + n] = the prompt followed by the new tokens, a finished row
+        filled with pad_token_id, stopping when every row has emitted an EOS (int or list) or at the length limit.  B > 1 needs left
+        padding; a padded text-only batch is fine (positions come from the mask).  Any other generation argument raises
+        NotImplementedError naming it.  Works in train() and eval() mode; touches no gradient buffer."""
+        from . import generation as _generation
+        _generation._refuse_unsupported(rest)          # generation.generate's own keywords beyond this signature are not public here
+        return _generation.generate(self, input_ids, pixel_values=pixel_values, pixel_attention_mask=pixel_attention_mask,
+                                    attention_mask=attention_mask, max_new_tokens=max_new_tokens, max_length=max_length,
+                                    eos_token_id=eos_token_id, pad_token_id=pad_token_id, streamer=streamer, do_sample=do_sample,
+                                    num_beams=num_beams, **rest)
 
     def set_precision(self, precision):
         if precision != "bf16":

@@ -149,6 +149,7 @@ class LlavaForConditionalGeneration(ArenaModule):
         pixel_values: a tensor or the reference's list of per-sample tensors (None: text only).  B > 1 needs left padding.  Any other
         generation argument raises NotImplementedError naming it.  Works in train() and eval() mode; touches no gradient buffer."""
         from . import generation as _generation
+        _generation._refuse_unsupported(rest)          # generation.generate's own keywords beyond this signature are not public here
         return _generation.generate(self, input_ids, pixel_values=pixel_values, attention_mask=attention_mask,
                                     max_new_tokens=max_new_tokens, max_length=max_length, eos_token_id=eos_token_id,
                                     pad_token_id=pad_token_id, streamer=streamer, do_sample=do_sample, num_beams=num_beams, **rest)

@@ -4,6 +4,8 @@
     python tools/decode_bench.py --all [--layers 32] [--new-tokens 128] [--out profiles/generation_decode.json]
     python tools/decode_bench.py --kernels                 # per-kernel A/B on every step shape
     python tools/decode_bench.py --batch 8 --path new      # one end-to-end measurement (what --all runs in child processes)
+    python tools/decode_bench.py --family idefics3 --batch 1   # Idefics3 generate(): ms / token without an EOS and with a never-firing EOS
+                                                               # read back every k = 1, 4, 8, 16 steps, three repeats each (+ --markdown)
 
 Prompt = the headline sample (4 x 336^2 images + 512 tokens), B in {1, 8}, 128 new tokens.  The comparator is what the library offered
 before the decode kernels: the same step composed from the existing entries (`gemm_nt` at M = B, `rope_apply_`, `attn_fwd_cross` with one query row
@@ -202,8 +204,82 @@ def end_to_end(B, path, layers, n_new):
                 frac_of_achievable=round((wbytes + cbytes) / ms / 1e9 / HBM_ACHIEVABLE_TBS, 3), readback_ms_per_token=ms_rb, clock=_clock())
 
 
+def idefics3_generate(B, layers, n_new, repeats=3, intervals=(1, 4, 8, 16)):
+    """`Idefics3ForConditionalGeneration`'s generation loop end to end at the 8B Llama-3 geometry: a prompt of 4 images' worth of <image>
+    tokens + 512 text tokens, n_new new tokens.  ms / token = (end of generate - end of prefill) / (n_new - 1), `repeats` times for: no EOS
+    (the loop never reads back), then an EOS that never fires read back every k steps.  The rule for generation.EOS_CHECK_EVERY: the
+    smallest k whose median lies within the no-EOS loop's own max - min spread of the no-EOS median."""
+    import torch
+    from mantis_amd import generation as G
+    from mantis_amd.configuration_idefics3 import idefics3_8b_llama3
+    from mantis_amd.modeling_idefics3 import Idefics3ForConditionalGeneration
+    cfg = idefics3_8b_llama3()
+    cfg.text_config.num_hidden_layers = layers
+    model = Idefics3ForConditionalGeneration(cfg, device="cuda", seed=0)
+    model.eval()
+    vc = cfg.vision_config
+    n_tok = (vc.image_size // vc.patch_size // cfg.scale_factor) ** 2
+    n_img, n_text = 4, 512
+    g = torch.Generator().manual_seed(1)
+    T = n_img * n_tok + n_text
+    ids = torch.randint(1, 120000, (B, T), generator=g)
+    for j in range(n_img):
+        s = 8 + j * (n_tok + 24)
+        ids[:, s: s + n_tok] = cfg.image_token_id
+    am = torch.ones_like(ids)
+    pix = torch.randn(B, n_img, 3, vc.image_size, vc.image_size, generator=g)
+    eos = cfg.text_config.vocab_size - 1
+    marks = []
+    real_prefill = G.prefill
+
+    def timed_prefill(*a, **k):
+        r = real_prefill(*a, **k)
+        torch.cuda.synchronize()
+        marks.append(time.perf_counter())
+        return r
+    G.prefill = timed_prefill
+
+    def run(**kw):
+        t0 = time.perf_counter()
+        out = G.generate(model, ids, pixel_values=pix, attention_mask=am, max_new_tokens=n_new, **kw)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        if out.shape[1] != T + n_new or bool((out[:, T:] == eos).any()):
+            raise SystemExit(f"the EOS {eos} fired: this run does not measure a never-firing EOS")
+        return (t1 - marks[-1]) * 1e3 / (n_new - 1), (marks[-1] - t0) * 1e3
+    run()                                                                  # warm-up: allocator, first-step checks
+    rows = []
+    for name, kw in [("no EOS", {})] + [(f"k = {k}", dict(eos_token_id=eos, pad_token_id=cfg.pad_token_id, eos_check_every=k)) for k in intervals]:
+        r = [run(**kw) for _ in range(repeats)]
+        ms = [x[0] for x in r]
+        rows.append(dict(loop=name, ms_per_token=[round(x, 4) for x in ms], median=round(statistics.median(ms), 4),
+                         spread=round(max(ms) - min(ms), 4), prefill_ms=round(statistics.median(x[1] for x in r), 1)))
+    base = rows[0]
+    pick = next((int(r["loop"][4:]) for r in rows[1:] if r["median"] - base["median"] <= base["spread"]), None)
+    tc = cfg.text_config
+    d, I, V = tc.hidden_size, tc.intermediate_size, tc.vocab_size
+    wbytes = 2.0 * (layers * ((tc.num_attention_heads + 2 * tc.num_key_value_heads) * tc.head_dim * d + d * d + 3 * I * d) + V * d)
+    cbytes = 2.0 * 2 * layers * B * tc.num_key_value_heads * tc.head_dim * (T + n_new / 2)
+    return dict(family="idefics3", batch=B, layers=layers, prompt=T, new_tokens=n_new, rows=rows, smallest_k_within_spread=pick,
+                tbs_no_eos=round((wbytes + cbytes) / base["median"] / 1e9, 2), default_in_tree=G.EOS_CHECK_EVERY, clock=_clock())
+
+
+def _markdown(res):
+    out = [f"B = {res['batch']}, {res['layers']} layers, prompt {res['prompt']} tokens, {res['new_tokens']} new tokens; clock: {res['clock']}", "",
+           "| loop | ms / token (three repeats) | median | max - min | median - no-EOS median |", "|---|---|---|---|---|"]
+    base = res["rows"][0]["median"]
+    for r in res["rows"]:
+        out.append(f"| {r['loop']} | {', '.join(f'{x:.3f}' for x in r['ms_per_token'])} | {r['median']:.3f} | {r['spread']:.3f} | "
+                   f"{r['median'] - base:+.3f} |")
+    out += ["", f"no-EOS loop: {res['tbs_no_eos']} TB/s of weights + live cache per token; prefill {res['rows'][0]['prefill_ms']} ms; "
+                f"smallest k within the no-EOS spread: {res['smallest_k_within_spread']}"]
+    return "\n".join(out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--family", choices=("llava", "idefics3"), default="llava")
+    ap.add_argument("--markdown", action="store_true", help="--family idefics3: print the table as markdown after the JSON line")
     ap.add_argument("--all", action="store_true")
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--batch", type=int, default=1)
@@ -225,6 +301,15 @@ def main():
             line = [l for l in r.stdout.splitlines() if l.startswith("{") or l.startswith("[")][-1]
             res.append(json.loads(line))
             print(line, flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
+    if a.family == "idefics3":
+        res = idefics3_generate(a.batch, a.layers, a.new_tokens)
+        print(json.dumps(res), flush=True)
+        if a.markdown:
+            print(_markdown(res), flush=True)
         if a.out:
             with open(a.out, "w") as f:
                 json.dump(res, f, indent=1)
