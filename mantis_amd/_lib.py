@@ -115,6 +115,7 @@ def load():
     return lib
 
 
-def check(rc, what):
+def check(rc, what, *args):
+    """`what % args` names the call; the GEMM wrappers pass the arguments apart so that a launch that succeeds formats nothing."""
     if rc != 0:
-        raise MantisHipError(f"{what} failed: {ERRORS.get(rc, rc)} (rc={rc})")
+        raise MantisHipError(f"{what % args if args else what} failed: {ERRORS.get(rc, rc)} (rc={rc})")

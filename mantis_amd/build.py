@@ -17,7 +17,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 # attn_fwd64: the hand-placed instruction stream wants one VALU instruction per source operation (no v_pk_* packing of f32 pairs)
 EXTRA_FLAGS = {"attn_fwd64": ["-fno-slp-vectorize"]}
 HEADERS = ["common.h", "attn_common.h", "gemm_ring.h", "gemm_plan.h", "gemm_flags.h", "attn_fwd_body.inc", "attn_bwd_dq_body.inc", "attn_bwd_dkv_body.inc",
-           "attn_bwd_dkv_g4_body.inc", "attn_fwd64_body.inc"]
+           "attn_bwd_dkv_g4_body.inc", "attn_fwd64_body.inc",
+           "../../include/mantis_hip.h"]         # common.h and gemm_flags.h include the public header: a changed prototype rebuilds
 
 
 def _hipcc():

@@ -4,10 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define MANTIS_OK 0
-#define MANTIS_EINVAL (-1)
-#define MANTIS_EUNSUPPORTED (-2)
-#define MANTIS_ELAUNCH (-3)
+#include "../../include/mantis_hip.h"  // the C-ABI: every definition compiles against its declaration; the MANTIS_* return codes
 
 typedef unsigned short bf16_t;  // raw bits
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;

@@ -1,6 +1,7 @@
 // Flag bits and tile constants of the bf16 GEMM entry points (include/mantis_hip.h): plain defines, shared by the host-only planner
 // (gemm_plan.h) and the kernels (gemm_ring.h)
 #pragma once
+#include "../../include/mantis_hip.h"  // the MANTIS_* return codes (plain C: this header and gemm_plan.h stay host-only)
 #define BK 64
 #define EPI_BIAS 1
 #define EPI_ACT_SHIFT 1
@@ -23,8 +24,3 @@
 #define PAIR_NONE 0                         // two-column forward fusions of the ring16 / 176-row epilogue (see ring16_epilogue)
 #define PAIR_SWIGLU 1
 #define PAIR_ROPE 2
-#ifndef MANTIS_OK                           // the return codes of common.h, for a host build without it
-#define MANTIS_OK 0
-#define MANTIS_EINVAL (-1)
-#define MANTIS_EUNSUPPORTED (-2)
-#endif

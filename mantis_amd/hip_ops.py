@@ -15,9 +15,16 @@ ACT_KIND = {"gelu": 0, "gelu_pytorch_tanh": 1, "quick_gelu": 2, "silu": 3}
 GEMM_ACT = {None: 0, "gelu": 1, "gelu_pytorch_tanh": 2, "quick_gelu": 3}
 # Launch options (per-launch HIP events for bench.py, the optimizer's sum-of-squares collector, the GEMM scheduler's CU budget) come from
 # the caller's LaunchContext (mantis_amd/launch.py), installed by the engine for the duration of one step -- no module-level switches.
-CUS_SHIFT = 16               # bits 16-27 of the GEMM entry points' flags: the CU budget of that launch (include/mantis_hip.h)
-SK_INKERNEL = 16384          # flag: K-split remainder tiles reduced inside the GEMM kernel (round 4) instead of by the finishing kernel
-SHARED_GPU = 32768           # flag: RCCL collectives hold CUs beside this launch (LaunchContext.shared_gpu): no persistent GEMM workgroups
+# The `flags` word of the bf16 GEMM entry points, under the names of csrc/gemm_flags.h (tests/test_cabi_exports.py holds the values to it):
+EPI_BIAS, EPI_ACT_SHIFT, EPI_RESIDUAL, EPI_ACCUM, EPI_SWIGLU_BWD = 1, 1, 16, 32, 64
+EPI_VARIANT_SHIFT, EPI_A_KMAJOR, EPI_B_KMAJOR = 8, 4096, 8192       # bits 8-11: tile variant (0 = the library's choice)
+EPI_SK_INKERNEL = 16384      # K-split remainder tiles reduced inside the GEMM kernel (round 4) instead of by the finishing kernel
+EPI_SHARED_GPU = 32768       # RCCL collectives hold CUs beside this launch (LaunchContext.shared_gpu): no persistent GEMM workgroups
+EPI_CUS_SHIFT = 16           # bits 16-27: the CU budget of that launch
+# mantis_gemm_bf16_nt_fused takes no flags word: the same two switches travel in its `variant`, whose low bits hold the variant itself (where
+# `flags` holds the epilogue), so they sit at bits 6 and 7 there (csrc/gemm_plan.h, gemm_fused_choose); the CU budget keeps bits 16-27
+FUSED_SK_INKERNEL, FUSED_SHARED_GPU = 64, 128
+F8_EPI_BIAS, F8_EPI_RESIDUAL, F8_EPI_ACCUM, F8_EPI_VECSCALE = 1, 16, 32, 128      # mantis_gemm_fp8_nt's flags (csrc/gemm_fp8.hip)
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -67,6 +74,29 @@ def _gemm_workspace():
 
 
 # ----------------------------------------------------------------------------------------------------------- GEMM family
+def _launch_bits(ctx, shared, variant=0, cus=None, sk_inkernel=False):
+    """The part of the flags word every bf16 GEMM launch shares: tile variant, CU budget (the context's unless `cus` overrides it), in-kernel
+    remainder reduction and, where the entry takes it (`shared`: False for _sumsq and _tn_pair, which reject flags they do not know), the
+    shared-GPU bit.  Positional arguments: ~1700 launches per 8B step come through here."""
+    return ((variant << EPI_VARIANT_SHIFT) | ((ctx.gemm_cus if cus is None else cus) << EPI_CUS_SHIFT) | (EPI_SK_INKERNEL if sk_inkernel else 0)
+            | (EPI_SHARED_GPU if shared and ctx.shared_gpu else 0))
+
+
+def _timer_start():
+    """Opens the per-launch bracket of LaunchContext.timer: a start event on torch's current stream (== the stream handed to the kernel)."""
+    e0 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return e0
+
+
+def _timer_stop(prof, e0, kernel, flops, nbytes, tag=None):
+    """Closes the bracket and leaves the launch's record (algorithmic flops and bytes): the bf16 GEMM family gives a tag (M, N, K, layout,
+    epilogue) and gets (kernel, flops, bytes, start, end, tag, stream); without one the record ends after the two events (fp8, skinny)."""
+    e1 = torch.cuda.Event(enable_timing=True)
+    e1.record()
+    prof.append((kernel, flops, nbytes, e0, e1) if tag is None else (kernel, flops, nbytes, e0, e1, tag, _stream()))
+
+
 def gemm_nt(a, b, bias=None, act=None, residual=None, out=None, accumulate=False, n_valid=None, k=None, ldc=None, variant=0,
             a_kmajor=False, b_kmajor=False, cus=None, sk_inkernel=False):
     """out[M,N] = epi(A . B^T) with A = a[M,K] (or a[K,M] if a_kmajor), B = b[N,K] (or b[K,N] if b_kmajor).
@@ -87,29 +117,24 @@ def gemm_nt(a, b, bias=None, act=None, residual=None, out=None, accumulate=False
         out = torch.empty((M, N if ldc is None else ldc), dtype=BF16, device=a.device)   # ldc > N: padded row stride
     else:
         _chk2d(out, "out")
-    C = out
     ctx = _launch()
     if cus is not None and not 0 <= int(cus) <= 4095:
         raise ValueError(f"cus must be in [0, 4095] (0 = the library's default), got {cus}")
-    flags = (1 if bias is not None else 0) | (GEMM_ACT[act] << 1) | (16 if residual is not None else 0) | (32 if accumulate else 0) \
-        | (variant << 8) | (4096 if a_kmajor else 0) | (8192 if b_kmajor else 0) | ((ctx.gemm_cus if cus is None else cus) << CUS_SHIFT) \
-        | (SK_INKERNEL if sk_inkernel else 0) | (SHARED_GPU if ctx.shared_gpu else 0)
+    flags = ((EPI_BIAS if bias is not None else 0) | (GEMM_ACT[act] << EPI_ACT_SHIFT) | (EPI_RESIDUAL if residual is not None else 0)
+             | (EPI_ACCUM if accumulate else 0) | (EPI_A_KMAJOR if a_kmajor else 0) | (EPI_B_KMAJOR if b_kmajor else 0)
+             | _launch_bits(ctx, True, variant, cus, sk_inkernel))
     prof = ctx.timer
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()          # torch's current stream == the stream handed to the kernel below
+    e0 = _timer_start() if prof is not None else None
     wsp, wsn = _gemm_workspace()
-    rc = _L.mantis_gemm_bf16_nt(_p(a), a.stride(0), _p(b), b.stride(0), _p(C), C.stride(0), M, N, K, _p(bias), _p(residual),
+    rc = _L.mantis_gemm_bf16_nt(_p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), M, N, K, _p(bias), _p(residual),
                                 0 if residual is None else residual.stride(0), flags, wsp, wsn, _stream())
-    _lib.check(rc, f"gemm M={M} N={N} K={K} akm={a_kmajor} bkm={b_kmajor}")
+    _lib.check(rc, "gemm M=%s N=%s K=%s akm=%s bkm=%s", M, N, K, a_kmajor, b_kmajor)       # formatted only on failure
     if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
         # algorithmic bytes: both operands read once, the result written once (+ residual / accumulate read)
         by = 2.0 * (M * K + N * K + M * N * (1 + (residual is not None) + bool(accumulate)))
         lay = ("T" if a_kmajor else "N") + ("N" if b_kmajor else "T")      # A^T? / B as [N,K] ("T": B^T is applied) -- NT = forward, NN = dX, TN = dW
         epi = "+".join(x for x, on in (("bias", bias is not None), (str(act), act is not None), ("res", residual is not None), ("acc", accumulate)) if on)
-        prof.append(("gemm_nt_kernel", 2.0 * M * N * K, by, e0, e1, (M, N, K, lay, epi or "-"), _stream()))
+        _timer_stop(prof, e0, "gemm_nt_kernel", 2.0 * M * N * K, by, (M, N, K, lay, epi or "-"))
     return out
 
 
@@ -190,20 +215,16 @@ def gemm_fp8_nt(a8, a_dequant, b8, b_dequant, fmt_a=FP8_E4M3, bias=None, residua
         raise ValueError(f"gemm_fp8_nt rowwise: dequant vectors {a_dequant.numel()} / {b_dequant.numel()} for M={M} N={N}")
     if not rowwise and (a_dequant.numel() != 1 or b_dequant.numel() != 1):
         raise ValueError("gemm_fp8_nt: per-tensor dequant factors are fp32[1]; pass rowwise=True for vectors")
-    flags = ((1 if bias is not None else 0) | (16 if residual is not None else 0) | (32 if accumulate else 0) | (128 if rowwise else 0) |
-             (variant << 8))
+    flags = ((F8_EPI_BIAS if bias is not None else 0) | (F8_EPI_RESIDUAL if residual is not None else 0) | (F8_EPI_ACCUM if accumulate else 0)
+             | (F8_EPI_VECSCALE if rowwise else 0) | (variant << 8))
     prof = _launch().timer
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _timer_start() if prof is not None else None
     rc = _L.mantis_gemm_fp8_nt(_p(a8), a8.stride(0), _p(b8), b8.stride(0), _p(out), out.stride(0), M, N, K, _p(a_dequant), _p(b_dequant),
                                fmt_a, _p(bias), _p(residual), 0 if residual is None else residual.stride(0), flags, _stream())
-    _lib.check(rc, f"gemm_fp8 M={M} N={N} K={K}")
+    _lib.check(rc, "gemm_fp8 M=%s N=%s K=%s", M, N, K)
     if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        prof.append(("gemm_fp8_nt_kernel", 2.0 * M * N * K, 1.0 * (M * K + N * K) + 2.0 * M * N * (1 + (residual is not None) + bool(accumulate)),
-                     e0, e1))
+        _timer_stop(prof, e0, "gemm_fp8_nt_kernel", 2.0 * M * N * K,
+                    1.0 * (M * K + N * K) + 2.0 * M * N * (1 + (residual is not None) + bool(accumulate)))
     return out
 
 
@@ -217,16 +238,12 @@ def gemm_fp8_dx_swiglu(dy8, dy_dequant, wt8, w_dequant, gu, fmt_a=FP8_E5M2):
     dgu = torch.empty_like(gu)
     amax = torch.empty(1, dtype=torch.float32, device=gu.device)
     prof = _launch().timer
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _timer_start() if prof is not None else None
     rc = _L.mantis_gemm_fp8_dx_swiglu(_p(dy8), dy8.stride(0), _p(wt8), wt8.stride(0), _p(dgu), dgu.stride(0), M, I, d, _p(dy_dequant),
                                       _p(w_dequant), fmt_a, _p(gu), gu.stride(0), _p(amax), _stream())
-    _lib.check(rc, f"gemm_fp8+swiglu_bwd M={M} I={I} d={d}")
+    _lib.check(rc, "gemm_fp8+swiglu_bwd M=%s I=%s d=%s", M, I, d)
     if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        prof.append(("gemm_fp8_nt_kernel", 2.0 * M * I * d, 1.0 * (M * d + I * d) + 2.0 * 4 * M * I, e0, e1))
+        _timer_stop(prof, e0, "gemm_fp8_nt_kernel", 2.0 * M * I * d, 1.0 * (M * d + I * d) + 2.0 * 4 * M * I)
     return dgu, amax
 
 
@@ -280,28 +297,26 @@ def _gemm_fused(a, b, out, mode, aux0, aux1, aux_ld, aux_n, bias, variant, extra
     """mantis_gemm_bf16_nt_fused; returns False when the library declines the shape (the caller runs the unfused launches)."""
     M, K = a.shape
     N = b.shape[0]
-    prof = _launch().timer
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
+    ctx = _launch()
+    prof = ctx.timer
+    e0 = _timer_start() if prof is not None else None
     wsp, wsn = _gemm_workspace()
     rc = _L.mantis_gemm_bf16_nt_fused(_p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), M, N, K, _p(bias), mode, _p(aux0),
-                                      _p(aux1), aux_ld, aux_n, variant | (_launch().gemm_cus << CUS_SHIFT) | (128 if _launch().shared_gpu else 0),
+                                      _p(aux1), aux_ld, aux_n, variant | (ctx.gemm_cus << EPI_CUS_SHIFT) | (FUSED_SHARED_GPU if ctx.shared_gpu else 0),
                                       wsp, wsn, _stream())
     if rc == -2:
         return False
-    _lib.check(rc, f"gemm_fused mode={mode} M={M} N={N} K={K}")
+    _lib.check(rc, "gemm_fused mode=%s M=%s N=%s K=%s", mode, M, N, K)
     if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        prof.append(("gemm_nt_kernel", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N) + extra_bytes, e0, e1,
-                     (M, N, K, "NT", ("swiglu" if mode == 1 else "rope") + ("+bias" if bias is not None else "")), _stream()))
+        _timer_stop(prof, e0, "gemm_nt_kernel", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N) + extra_bytes,
+                    (M, N, K, "NT", ("swiglu" if mode == 1 else "rope") + ("+bias" if bias is not None else "")))
     return True
 
 
 def linear_gu_swiglu(x, w_gu, variant=0, amax_parts=None):
     """(gu [M, 2I], a [M, I]) = (x . [gate | up]^T, silu(gate) * up): the SwiGLU activation runs in the epilogue of the projection (one
-    launch, the 2I-wide result is not read back); shapes the fused kernel declines take gemm_nt + swiglu_fwd (same results)."""
+    launch, the 2I-wide result is not read back); shapes the fused kernel declines take gemm_nt + swiglu_fwd (same results).
+    variant: 0, or 13 / 14 / 15 forced, | FUSED_SK_INKERNEL (tests); the same in linear_qkv_rope."""
     _chk2d(x, "x"), _chk2d(w_gu, "w_gu")
     M, I2 = x.shape[0], w_gu.shape[0]
     if FUSE_FWD_EPILOGUES and amax_parts is None and I2 % 256 == 0:
@@ -336,20 +351,15 @@ def linear_dx_swiglu(dy, w_down, gu, variant=0, sk_inkernel=False):
     if gu.shape != (M, 2 * I) or w_down.shape[0] != d:
         raise ValueError(f"linear_dx_swiglu: dy {tuple(dy.shape)} w_down {tuple(w_down.shape)} gu {tuple(gu.shape)}")
     dgu = torch.empty_like(gu)
-    prof = _launch().timer
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
+    ctx = _launch()
+    prof = ctx.timer
+    e0 = _timer_start() if prof is not None else None
     wsp, wsn = _gemm_workspace()
     rc = _L.mantis_gemm_bf16_nt(_p(dy), dy.stride(0), _p(w_down), w_down.stride(0), _p(dgu), dgu.stride(0), M, I, d, None, _p(gu),
-                                gu.stride(0), 64 | 8192 | (variant << 8) | (_launch().gemm_cus << CUS_SHIFT) | (SK_INKERNEL if sk_inkernel else 0)
-                                | (SHARED_GPU if _launch().shared_gpu else 0), wsp, wsn,
-                                _stream())
-    _lib.check(rc, f"gemm+swiglu_bwd M={M} I={I} d={d}")
+                                gu.stride(0), EPI_SWIGLU_BWD | EPI_B_KMAJOR | _launch_bits(ctx, True, variant, None, sk_inkernel), wsp, wsn, _stream())
+    _lib.check(rc, "gemm+swiglu_bwd M=%s I=%s d=%s", M, I, d)
     if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        prof.append(("gemm_nt_kernel", 2.0 * M * I * d, 2.0 * (M * d + I * d + 4 * M * I), e0, e1, (M, I, d, "NN", "swiglu_bwd"), _stream()))
+        _timer_stop(prof, e0, "gemm_nt_kernel", 2.0 * M * I * d, 2.0 * (M * d + I * d + 4 * M * I), (M, I, d, "NN", "swiglu_bwd"))
     return dgu
 
 
@@ -368,18 +378,15 @@ def linear_dw(dy, x, grad_w, accumulate):
         slot = col.take(grad_w, tiles)
         if slot is not None:
             prof = ctx.timer
-            if prof is not None:
-                e0 = torch.cuda.Event(enable_timing=True)
-                e0.record()
+            e0 = _timer_start() if prof is not None else None
             wsp, wsn = _gemm_workspace()
             rc = _L.mantis_gemm_bf16_nt_sumsq(_p(a), a.stride(0), _p(x), x.stride(0), _p(grad_w), grad_w.stride(0), M, N, Kd,
-                                              (32 if accumulate else 0) | 4096 | 8192 | (ctx.gemm_cus << CUS_SHIFT), slot, wsp, wsn, _stream())
+                                              (EPI_ACCUM if accumulate else 0) | EPI_A_KMAJOR | EPI_B_KMAJOR | _launch_bits(ctx, False),
+                                              slot, wsp, wsn, _stream())
             if rc == 0:
                 if prof is not None:
-                    e1 = torch.cuda.Event(enable_timing=True)
-                    e1.record()
-                    prof.append(("gemm_nt_kernel", 2.0 * M * N * Kd, 2.0 * (M * Kd + N * Kd + M * N * (1 + bool(accumulate))), e0, e1,
-                                 (M, N, Kd, "TN", "sumsq" + ("+acc" if accumulate else "")), _stream()))
+                    _timer_stop(prof, e0, "gemm_nt_kernel", 2.0 * M * N * Kd, 2.0 * (M * Kd + N * Kd + M * N * (1 + bool(accumulate))),
+                                (M, N, Kd, "TN", "sumsq" + ("+acc" if accumulate else "")))
                 return
             if rc != -2:
                 _lib.check(rc, f"gemm_sumsq M={M} N={N} K={Kd}")
@@ -411,35 +418,31 @@ def linear_dw_pair(dy1, x1, grad_w1, dy2, x2, grad_w2, accumulate):
     col = ctx.dw_sumsq
     s1 = s2 = None
     if col is not None:
-        t1, t2 = ((M1 + 255) // 256) * (N1 // 256), ((M2 + 255) // 256) * (N2 // 256)
+        t1, t2 = ((M1 + 255) // 256) * (N1 // 256), ((M2 + 255) // 256) * (N2 // 256)      # tiles of each result (N % 256 == 0 here)
         s1 = col.take(grad_w1, t1)
         s2 = col.take(grad_w2, t2) if s1 is not None else None
         if s1 is not None and s2 is None:
             col.give_back(grad_w1, t1)
             s1 = None
     prof = ctx.timer
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _timer_start() if prof is not None else None
     rc = _L.mantis_gemm_bf16_tn_pair(_p(a1), a1.stride(0), _p(x1), x1.stride(0), _p(grad_w1), grad_w1.stride(0), M1, N1, s1,
                                      _p(a2), a2.stride(0), _p(x2), x2.stride(0), _p(grad_w2), grad_w2.stride(0), M2, N2, s2,
-                                     Kd, (32 if accumulate else 0) | (ctx.gemm_cus << CUS_SHIFT), _stream())
+                                     Kd, (EPI_ACCUM if accumulate else 0) | _launch_bits(ctx, False), _stream())
     if rc == -2:
         if s1 is not None:
-            col.give_back(grad_w2, ((M2 + 255) // 256) * (N2 // 256))
-            col.give_back(grad_w1, ((M1 + 255) // 256) * (N1 // 256))
+            col.give_back(grad_w2, t2)
+            col.give_back(grad_w1, t1)
         linear_dw(dy1, x1, grad_w1, accumulate)
         linear_dw(dy2, x2, grad_w2, accumulate)
         return
-    _lib.check(rc, f"gemm_tn_pair {M1}x{N1} + {M2}x{N2} K={Kd}")
+    _lib.check(rc, "gemm_tn_pair %sx%s + %sx%s K=%s", M1, N1, M2, N2, Kd)
     if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
         fl = 2.0 * Kd * (M1 * N1 + M2 * N2)
         by = 2.0 * (Kd * (M1 + N1 + M2 + N2) + (M1 * N1 + M2 * N2) * (1 + bool(accumulate)))
         # one table row for the launch: the first problem's shape, the second named in the epilogue column (FLOPs and bytes are the pair's)
-        prof.append(("gemm_nt_kernel", fl, by, e0, e1, (M1, N1, Kd, "TN", f"paired with {M2}x{N2}x{Kd}" + ("+sumsq" if s1 is not None else "")
-                                                        + ("+acc" if accumulate else "")), _stream()))
+        _timer_stop(prof, e0, "gemm_nt_kernel", fl, by, (M1, N1, Kd, "TN", f"paired with {M2}x{N2}x{Kd}" + ("+sumsq" if s1 is not None else "")
+                                                         + ("+acc" if accumulate else "")))
 
 
 def sum_f32(x, out, accumulate=False):
@@ -652,16 +655,12 @@ def linear_skinny(x, w, bias=None, residual=None, n_valid=None, ldc=None, out=No
     else:
         _chk2d(out, "out")
     prof = _launch().timer
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _timer_start() if prof is not None else None
     rc = _L.mantis_linear_skinny_bf16(_p(x), x.stride(0), _p(w), w.stride(0), _p(out), out.stride(0), M, N, K, _p(bias), _p(residual),
                                       0 if residual is None else residual.stride(0), _stream())
     _lib.check(rc, f"linear_skinny M={M} N={N} K={K}")
     if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        prof.append(("linear_skinny_kernel", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N * (1 + (residual is not None))), e0, e1))
+        _timer_stop(prof, e0, "linear_skinny_kernel", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N * (1 + (residual is not None))))
     return out
 
 

@@ -17,7 +17,8 @@ class LaunchContext:
     dw_sumsq:    None, or the optimizer's collector (`optim.FusedAdamW.begin_fold()`): every weight-gradient GEMM then also leaves the
                  sum of squares of what it stored (mantis_gemm_bf16_nt_sumsq)
     shared_gpu:  True when long-running kernels of other queues (RCCL collectives) hold compute units beside the step's kernels: the GEMM
-                 entry points get flag 32768 (one tile per workgroup in the 176-row kernel); MantisHipTrainer sets it with an active reducer
+                 entry points get hip_ops.EPI_SHARED_GPU (one tile per workgroup in the 176-row kernel); MantisHipTrainer sets it with an
+                 active reducer
     gemm_cus:    compute units the GEMM tile scheduler plans for (0 = the library's default: MANTIS_GEMM_CUS or the whole device);
                  with C RCCL channels active a data-parallel trainer plans for #CU - C"""
     __slots__ = ("timer", "dw_sumsq", "gemm_cus", "shared_gpu")

@@ -2410,7 +2410,7 @@ def check_gemm_sk_finish():
     their last arriver inside the GEMM kernel, and the remainder round is BALANCED (SkPlan: ranges of T / #CU K-steps, a range that crosses a
     tile boundary is two workgroups) where the equal split would leave CUs idle.
       (1) where both paths use the same partition (384 tiles on 256 CUs: 128 remainder tiles x 2 parts; 528 tiles: 16 x 8 parts) the finishing
-          kernel is BIT-IDENTICAL to the in-kernel reduction (flag 16384 / variant bit 64): every epilogue kind, both ring16 geometries;
+          kernel is BIT-IDENTICAL to the in-kernel reduction (EPI_SK_INKERNEL / FUSED_SK_INKERNEL of the fused entry's variant): every epilogue kind, both ring16 geometries;
       (2) the balanced plan (352 / 330 / 72 tiles): reproducible bit for bit, every row within the bf16 bar of the oracle, and within 2e-3 of
           the equal-split result (same products, another fp32 summation order); fused epilogues and the sum of squares included."""
     import ctypes
@@ -2465,12 +2465,12 @@ def check_gemm_sk_finish():
         from mantis_amd.decoder import inv_freq
         cos, sin = k.rope_table(pos, inv_freq(128, 5e5).to(DEV))
         q1 = k.linear_qkv_rope(x, wq, None, cos, sin, 40, 128, variant=v)
-        q2 = k.linear_qkv_rope(x, wq, None, cos, sin, 40, 128, variant=v | 64)
+        q2 = k.linear_qkv_rope(x, wq, None, cos, sin, 40, 128, variant=v | k.FUSED_SK_INKERNEL)
         assert torch.equal(q1, q2), f"q|k|v + RoPE: finishing kernel != in-kernel reduction (v{v})"
         wg = rnd(2 * 1920, 4096, seed=98, scale=0.02).to(DEV)           # N = 3840: 22 x 15 = 330 tiles -> 74 remainder tiles
         g1, a1 = k.linear_gu_swiglu(x, wg, variant=v)
         g1b, a1b = k.linear_gu_swiglu(x, wg, variant=v)
-        g2, a2 = k.linear_gu_swiglu(x, wg, variant=v | 64)
+        g2, a2 = k.linear_gu_swiglu(x, wg, variant=v | k.FUSED_SK_INKERNEL)
         assert torch.equal(g1, g1b) and torch.equal(a1, a1b)
         close(g1, g2, 2e-3, f"gate|up + SwiGLU, balanced vs equal split (v{v})")
         close(a1, a2, 4e-3, f"silu(gate) * up, balanced vs equal split (v{v})")
@@ -2486,12 +2486,12 @@ def check_gemm_sk_finish():
         a, b = rnd(K_, Mm, seed=102, scale=0.5).to(DEV), rnd(K_, Nn, seed=103, scale=0.5).to(DEV)
         tiles = ((Mm + 255) // 256) * ((Nn + 255) // 256)
         got = []
-        for ink in (0, 16384, 0):
+        for ink in (0, k.EPI_SK_INKERNEL, 0):
             c = torch.empty(Mm, Nn, dtype=BF, device=DEV)
             ts = torch.full((tiles,), float("nan"), dtype=torch.float32, device=DEV)
             wsp, wsn = k._gemm_workspace()
             rc = L.mantis_gemm_bf16_nt_sumsq(ctypes.c_void_p(a.data_ptr()), a.stride(0), ctypes.c_void_p(b.data_ptr()), b.stride(0),
-                                             ctypes.c_void_p(c.data_ptr()), c.stride(0), Mm, Nn, K_, 4096 | 8192 | (v << 8) | ink,
+                                             ctypes.c_void_p(c.data_ptr()), c.stride(0), Mm, Nn, K_, k.EPI_A_KMAJOR | k.EPI_B_KMAJOR | (v << k.EPI_VARIANT_SHIFT) | ink,
                                              ctypes.c_void_p(ts.data_ptr()), wsp, wsn, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
             assert rc == 0
             torch.cuda.synchronize()

@@ -89,7 +89,7 @@ def test_two_trainers_keep_their_own_options(monkeypatch):
 
 def test_an_active_reducer_switches_persistent_gemm_workgroups_off():
     """Round 6: a persistent GEMM workgroup that has to wait for a compute unit an RCCL channel holds would walk its whole static tile list late;
-    with an ACTIVE gradient reducer the trainer's launches therefore carry `shared_gpu` (flag 32768: one tile per workgroup in the 176-row
+    with an ACTIVE gradient reducer the trainer's launches therefore carry `shared_gpu` (EPI_SHARED_GPU: one tile per workgroup in the 176-row
     kernel, same results).  No reducer / an inactive one (world size 1): persistent."""
     from mantis_amd.launch import LaunchContext
     from mantis_amd.trainer import MantisHipTrainer

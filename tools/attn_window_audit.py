@@ -74,7 +74,7 @@ def main():
     tmp = tempfile.mkdtemp()
     base_dir = os.path.join(tmp, "base")
     os.makedirs(base_dir)
-    arch = subprocess.run(["git", "-C", ROOT, "archive", base, "mantis_amd/csrc"], capture_output=True, check=True).stdout
+    arch = subprocess.run(["git", "-C", ROOT, "archive", base, "mantis_amd/csrc", "include"], capture_output=True, check=True).stdout
     subprocess.run(["tar", "-x", "-C", base_dir], input=arch, check=True)
     ok = True
     for name in sources:
